@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the ZPAQ context-mixing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--blocks B --block-bytes S --kind text --method 5]
+    python bench.py --gpus N --steps K --warmup W [--blocks B --block-bytes S --kind text --method 5] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path (Predictor init + predict/update/encode of
 every bit) over one batch of B synthetic blocks per GPU, inputs already resident
@@ -396,6 +396,36 @@ def dry_run_bench(a):
         dist.destroy_process_group()
 
 
+DUMP_SEED = 20240917            # fixed: the same offsets are sampled in every run and every build
+DUMP_SAMPLE_BYTES = 8 << 20      # sampled output bytes (float32: 32 MB), plus 32 B of results per block
+
+
+def dump_outputs(path, out, res, region):
+    """--dump-outputs: what the caller of zpq_code_device_multi received from the last timed step, as .npy files.
+
+    block_results.npy  float64 [nb, 4]: the zpq_block_result of every block (out_len, consumed, status, steps).
+    output_sample.npy  float32 [nb, k]: the byte at k fixed offsets (seeded, the same for every block) of every block's
+                       output row `out` (uint8 [nb, >= region]); -1 where the offset lies at or past the block's out_len
+                       (what the row holds there is undefined: include/zpaq_amd.h).
+    output_offsets.npy float64 [k]:     those offsets.
+    The inputs are a pure function of the arguments (zpaq_amd.corpus), so two builds can be compared file for file."""
+    import torch
+    nb = res.shape[0]
+    if nb > (1 << 19):         # 16 MB of results + 32 MB of sample: within 64 MB in all
+        sys.exit(f"bench.py: --dump-outputs: {nb} blocks do not fit the 64 MB the dump may take")
+    k = min(region, max(1, DUMP_SAMPLE_BYTES // max(nb, 1)))
+    offs = np.sort(np.random.default_rng(DUMP_SEED).choice(region, size=k, replace=False))
+    col = torch.from_numpy(offs).to(out.device)
+    sample = out[:, col].to(torch.float32)
+    sample[col[None, :] >= res[:, 0].to(torch.int64)[:, None]] = -1.0
+    r = res.cpu().numpy().astype(np.int64)
+    r[:, [0, 1, 3]] &= 0xFFFFFFFF          # the unsigned fields (status stays signed)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "block_results.npy"), r.astype(np.float64))
+    np.save(os.path.join(path, "output_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(path, "output_offsets.npy"), offs.astype(np.float64))
+
+
 def machine_code_sha256(path):
     """sha256 over the .text and .rodata bytes of the gfx950 code object inside a clang offload bundle (or a bare ELF):
     what the GPU executes, without the bundle's ids and the notes that change with the name of the source file."""
@@ -481,7 +511,11 @@ def main():
                          "sharded over them (no torch.distributed)")
     ap.add_argument("--dry-run", action="store_true",
                     help="the N-rank flow on CPU: gloo, a method without a model (scatter, code, gather, one line with dist_ms); no GPU needed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's blocks) to DIR/*.npy: see dump_outputs()")
     a = ap.parse_args()
+    if a.dump_outputs and (a.dry_run or a.in_library):
+        sys.exit("bench.py: --dump-outputs covers the device-resident path, not --dry-run or --in-library")
     if a.cpu_seconds is None:
         a.cpu_seconds = 15.0 if a.gpus == 1 else 0.0
     if a.dry_run:
@@ -797,6 +831,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if a.dump_outputs and rank == 0 and a.mode == "encode":
+        dump_outputs(a.dump_outputs, d_out, d_res, cap)
     persistent = bool(L.zpq_last_persistent()) if a.mode == "encode" else None
     res = d_res.cpu().numpy()[:nb]
     out_len, status = res[:, 0].astype(np.int64), res[:, 2]
@@ -834,6 +870,8 @@ def main():
         cols = torch.arange(stride_in, device=dev)[None, :] < torch.tensor(in_len, device=dev)[:, None]
         dec_ok = dec_ok and bool(((back == d_in) | ~cols).all())
         dec_info = {"elapsed": delapsed, "code_ms": dcode_ms, "ok": dec_ok}
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, back, r2, stride_in)
         del back
     if a.distribute and world > 1:
         from zpaq_amd import dist as zd

@@ -152,17 +152,17 @@ def test_decompress_n_decodes_a_prefix_on_the_device(tmp_path, gpu):
 
 
 def _build_both(tmp_path, source, name):
-    """One driver source against this library's libzpaq.h + .so, and against the reference's libzpaq.h + libzpaq.cpp."""
-    ref_dir = "/root/reference"
-    if not os.path.exists(os.path.join(ref_dir, "libzpaq.cpp")):
-        pytest.skip("reference sources not present")
+    """One driver source against this library's libzpaq.h + .so, and against the reference's libzpaq.h + libzpaq.cpp
+    (the latter built with the checkers: oracle/Makefile `drivers`, oracle/_ref/<name>_driver_ref)."""
+    theirs = os.path.join(ROOT, "oracle", "_ref", name + "_driver_ref")
+    if not os.path.exists(theirs):
+        pytest.skip("oracle/_ref drivers not built (no reference sources where the checkers were built)")
     drv = os.path.join(ROOT, "tests", "cpp", source)
-    mine, theirs = str(tmp_path / (name + "_mine")), str(tmp_path / (name + "_ref"))
-    for cmd in (["g++", "-O1", "-std=c++17", drv, "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "zpaq_amd"), "-lzpaq_amd",
-                 "-Wl,-rpath," + os.path.join(ROOT, "zpaq_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", mine],
-                ["g++", "-O1", "-std=c++17", "-DNDEBUG", "-Dunix", drv, "-I" + ref_dir, os.path.join(ref_dir, "libzpaq.cpp"), "-pthread", "-o", theirs]):
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
+    mine = str(tmp_path / (name + "_mine"))
+    r = subprocess.run(["g++", "-O1", "-std=c++17", drv, "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "zpaq_amd"),
+                        "-lzpaq_amd", "-Wl,-rpath," + os.path.join(ROOT, "zpaq_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", mine],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
     return mine, theirs
 
 
