@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the ZPAQ context-mixing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--blocks B --block-bytes S --kind text --method 5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--blocks B --block-bytes S --kind text --method 5] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path (Predictor init + predict/update/encode of
 every bit) over one batch of B synthetic blocks per GPU, inputs already resident
@@ -19,13 +19,21 @@ units of the pipelined encoder stop contending for the memory pipeline
 
 Prints ONE JSON line (rank 0).  `roofline` prices the coding launch sequence
 against HBM (achieved = algorithmic model-state bytes per step / its duration
-measured with hipEvents on the launch stream); `cpu_baseline` times the
-reference libzpaq (oracle/_ref, kind "reference") or, if that was not built,
-our C oracle (kind "port") on a bounded sample of the same blocks on this
-box's host cores, and every archive the reference produced is compared with
-ours by SHA-1; `api` is the same batch through the drop-in API on HOST buffers
-(method expansion + SHA-1 + H2D + kernels + D2H + framing), outside the timed
-region.
+measured with hipEvents on the launch stream).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked
+and prints the line.  Everything else the benchmark measures or checks runs
+only with --full (or when its own option asks for it): every block decoded
+back on the device; every coded payload against the reference's SHA-1s
+(tests/golden); `decode`, BASELINE configs[4]'s decoder; `api`, the same batch
+through the drop-in API on HOST buffers (method expansion + SHA-1 + H2D +
+kernels + D2H + framing); `configs1`, `legacy2` and `legacy3`, other
+configurations in child processes; `cpu_baseline`, which times the reference
+libzpaq (oracle/_ref, kind "reference") or, if that was not built, our C
+oracle (kind "port") on a bounded sample of the same blocks on this box's host
+cores and compares every archive the reference produced with ours by SHA-1;
+with N > 1, the gather of the coded blocks to rank 0.  All of it runs outside
+the timed region.
 """
 from __future__ import annotations
 
@@ -229,7 +237,7 @@ def in_library_bench(a, torch, z):
     plan = z.Plan(z.method_to_header(z.expand_method(a.method, host[0]))[0])
     algo = plan.algo_bytes_per_byte * float(total_blocks) * (bs + 1)
     value = float(total_blocks) * bs * a.steps / 1e6 / wall
-    back = z.decompress(archives[0], bs + 64) == host[0].tobytes()
+    back = a.verify_blocks != 0 and z.decompress(archives[0], bs + 64) == host[0].tobytes()
     line = {"metric": f"compress MB/s + bit-identical ratio, -m{a.method} over {a.blocks}x{_size_name(bs)} blocks",
             "value": value, "unit": "MB/s", "n_gpus": ndev, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": wall * 1e3 / max(a.steps, 1), "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
@@ -272,7 +280,7 @@ def configs1_leg(cpu_seconds, timeout_s=150.0):
     an {"error": ...} object: the headline line must survive its side legs."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--method", "3", "--kind", "lcg", "--blocks", "256", "--block-bytes", "262144",
-           "--decode-blocks", "0", "--configs1", "0", "--cpu-seconds", str(cpu_seconds)]
+           "--full", "--decode-blocks", "0", "--configs1", "0", "--cpu-seconds", str(cpu_seconds)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, cwd=ROOT)
@@ -308,7 +316,7 @@ def legacy_leg(level, cpu_seconds, timeout_s=240.0):
     shape = {2: ["--kind", "lcg", "--blocks", "256", "--block-bytes", "262144"],
              3: ["--kind", "text", "--blocks", "1024", "--block-bytes", "1048576"]}[level]
     cmd = [sys.executable, os.path.abspath(__file__), "--legacy-level", str(level)] + shape + \
-          ["--decode-blocks", "0", "--configs1", "0", "--legacy", "0", "--cpu-seconds", str(cpu_seconds)]
+          ["--full", "--decode-blocks", "0", "--configs1", "0", "--legacy", "0", "--cpu-seconds", str(cpu_seconds)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, cwd=ROOT)
@@ -481,29 +489,33 @@ def main():
                          "level 2 on configs[1]'s data, level 3 on configs[2]'s")
     ap.add_argument("--legacy", type=int, default=None,
                     help="1: both legacy configurations (mid.cfg over 256 x 256 KiB LCG, max.cfg over 1024 x 1 MiB text) as side objects "
-                         "`legacy2` / `legacy3` of the line, each run by a child process; default: on for the default headline run on one GPU")
+                         "`legacy2` / `legacy3` of the line, each run by a child process; default: on for the default headline run "
+                         "on one GPU with --full, off otherwise")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--cpu-seconds", type=float, default=None,
-                    help="wall budget of the cpu_baseline leg (0 = skip; default 15 on one GPU, 0 on several: the contract asks for the "
-                         "CPU baseline on rank 0 at N = 1 only)")
-    ap.add_argument("--api-blocks", type=int, default=-1,
-                    help="blocks of the end-to-end API leg on host buffers (-1 = the whole batch, 0 = skip)")
-    ap.add_argument("--verify-blocks", type=int, default=-1, help="blocks decoded back on the device (-1: every block of the batch)")
+                    help="wall budget of the cpu_baseline leg (0 = skip; default with --full 15 on one GPU, 0 on several: the "
+                         "contract asks for the CPU baseline on rank 0 at N = 1 only; 0 without --full)")
+    ap.add_argument("--api-blocks", type=int, default=None,
+                    help="blocks of the end-to-end API leg on host buffers (-1 = the whole batch, 0 = skip; default -1 with "
+                         "--full, 0 without)")
+    ap.add_argument("--verify-blocks", type=int, default=None,
+                    help="blocks decoded back on the device (-1: every block of the batch; default -1 with --full, 0 without)")
     ap.add_argument("--verify-bytes", type=int, default=0, help="how much of each of them (0: the whole block)")
     ap.add_argument("--kernel", type=int, default=0, help="zpq_set_kernel: 0 the engine's choice, 3 / 5 with --mode decode: one / two blocks per wavefront")
-    ap.add_argument("--decode-blocks", type=int, default=2048,
+    ap.add_argument("--decode-blocks", type=int, default=None,
                     help="blocks of the `decode` leg of an encode run on one GPU (BASELINE configs[4]'s operating point: one "
-                         "residency wave of the 8192-block archive = 2048 x 1 MiB), outside the timed region; 0 = skip")
+                         "residency wave of the 8192-block archive = 2048 x 1 MiB), outside the timed region; 0 = skip; "
+                         "default 2048 with --full, 0 without")
     ap.add_argument("--configs1", type=int, default=None,
                     help="1: BASELINE configs[1] (-m3 over 256 x 256 KiB LCG blocks) as a side object of the line, run by a child "
-                         "process after the other legs; default: on for the default headline run on one GPU, off otherwise")
+                         "process after the other legs; default: on for the default headline run on one GPU with --full, off otherwise")
     ap.add_argument("--decode-kind", default=None,
                     help="corpus of the decode leg: default 'mixed' (BASELINE configs[4] decodes configs[3]'s archive); the same as --kind reuses the timed run's payloads")
     ap.add_argument("--mode", choices=["encode", "decode"], default="encode",
                     help="decode = BASELINE configs[4]: time Decoder::decompress over the archive just produced")
     ap.add_argument("--distribute", dest="distribute", action="store_true", default=None,
-                    help="N>1 (default there): rank 0 generates the whole corpus and scatters it over RCCL; coded blocks are "
-                         "gathered back (timed separately as dist_ms; the hot path itself has no collective)")
+                    help="N>1 (default there): rank 0 generates the whole corpus and scatters it over RCCL; with --full the coded "
+                         "blocks are gathered back (both timed separately as dist_ms; the hot path itself has no collective)")
     ap.add_argument("--no-distribute", dest="distribute", action="store_false",
                     help="N>1: every rank generates its own blocks (no RCCL traffic but the barrier and the timing reduction)")
     ap.add_argument("--in-library", action="store_true",
@@ -513,11 +525,22 @@ def main():
                     help="the N-rank flow on CPU: gloo, a method without a model (scatter, code, gather, one line with dist_ms); no GPU needed")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0's blocks) to DIR/*.npy: see dump_outputs()")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything the benchmark measures or checks beside the headline figure, each leg at the default its "
+                         "option names: the device round trip of every block, the reference's SHA-1s, the decode and api legs, "
+                         "configs1 / legacy2 / legacy3, the CPU baselines, the gather of N > 1 ranks; without it a run only sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
     a = ap.parse_args()
     if a.dump_outputs and (a.dry_run or a.in_library):
         sys.exit("bench.py: --dump-outputs covers the device-resident path, not --dry-run or --in-library")
     if a.cpu_seconds is None:
-        a.cpu_seconds = 15.0 if a.gpus == 1 else 0.0
+        a.cpu_seconds = 15.0 if a.full and a.gpus == 1 else 0.0
+    if a.api_blocks is None:
+        a.api_blocks = -1 if a.full else 0
+    if a.verify_blocks is None:
+        a.verify_blocks = -1 if a.full else 0
+    if a.decode_blocks is None:
+        a.decode_blocks = 2048 if a.full else 0
     if a.dry_run:
         return dry_run_bench(a)
     if a.legacy_level:
@@ -867,13 +890,14 @@ def main():
             delapsed = zd.max_over_ranks(delapsed)
         r2h = r2.cpu().numpy()
         dec_ok = bool((r2h[:, 2] == 0).all() and (r2h[:, 0] == np.array(in_len)).all())
-        cols = torch.arange(stride_in, device=dev)[None, :] < torch.tensor(in_len, device=dev)[:, None]
-        dec_ok = dec_ok and bool(((back == d_in) | ~cols).all())
+        if a.full:          # every decoded byte against the coder's input
+            cols = torch.arange(stride_in, device=dev)[None, :] < torch.tensor(in_len, device=dev)[:, None]
+            dec_ok = dec_ok and bool(((back == d_in) | ~cols).all())
         dec_info = {"elapsed": delapsed, "code_ms": dcode_ms, "ok": dec_ok}
         if a.dump_outputs and rank == 0:
             dump_outputs(a.dump_outputs, back, r2, stride_in)
         del back
-    if a.distribute and world > 1:
+    if a.full and a.distribute and world > 1:
         from zpaq_amd import dist as zd
         host_out = d_out.cpu().numpy()
         mine_coded = [host_out[i, :int(out_len[i])].tobytes() for i in range(nb)]
@@ -1022,15 +1046,15 @@ def main():
         if one:
             line["one_gpu_same_workload"] = one
     if rank == 0:
-        # coded payloads of the timed run, for the identity check against the reference
+        # coded payloads of the timed run, for the cpu_baseline leg's identity check against the reference
         ncmp = min(nb, 512)
-        host_out = d_out[:ncmp].cpu().numpy()
+        host_out = d_out[:ncmp].cpu().numpy() if a.cpu_seconds > 0 else None
         # ... and EVERY block of the headline corpus against what the reference made of it, frozen in tests/golden/headline_sha1.json
         # (tests/golden/make_headline_golden.py: the unmodified libzpaq, run where /root/reference exists; nothing of this library
         # or of the oracle is involved): SHA-1 of the coded payload + terminator of the timed, device-resident run
         golden = None
         gpath = os.path.join(ROOT, "tests", "golden", "headline_sha1.json")
-        if a.mode == "encode" and a.kind == "text" and a.method == "5" and bs == (1 << 20) and first == 0 and os.path.exists(gpath):
+        if a.full and a.mode == "encode" and a.kind == "text" and a.method == "5" and bs == (1 << 20) and first == 0 and os.path.exists(gpath):
             gj = json.load(open(gpath))["blocks"]
             ng = min(nb, len(gj))
             bad = []
@@ -1047,7 +1071,7 @@ def main():
                               "frozen in tests/golden/headline_sha1.json"}
             line["reference_identity"] = golden
         lpath = os.path.join(ROOT, "tests", "golden", "legacy_sha1.json")
-        if a.mode == "encode" and a.legacy_level and first == 0 and os.path.exists(lpath):
+        if a.full and a.mode == "encode" and a.legacy_level and first == 0 and os.path.exists(lpath):
             lj = json.load(open(lpath))["levels"].get(str(a.legacy_level))
             if lj and lj["block_bytes"] == bs and lj["corpus"].startswith(f"zpaq_amd.corpus.block('{a.kind}'"):
                 gj = lj["blocks"]
@@ -1102,10 +1126,10 @@ def main():
                            "ms": {"library_total": ph[0], "host_front": ph[1], "device_call": ph[2], "stitch": ph[3],
                                   "kernel_init": ph[4], "kernel_code": ph[5], "python_wall": wall * 1e3,
                                   "library_total_first_call": first_ms}}
-        want_c1 = a.configs1 if a.configs1 is not None else int(world == 1 and a.mode == "encode" and a.method == "5" and a.kind == "text"
-                                                                and nb == 1024 and bs == (1 << 20))
-        want_legacy = a.legacy if a.legacy is not None else int(world == 1 and a.mode == "encode" and a.method == "5" and a.kind == "text"
-                                                                 and nb == 1024 and bs == (1 << 20))
+        want_c1 = a.configs1 if a.configs1 is not None else int(a.full and world == 1 and a.mode == "encode" and a.method == "5"
+                                                                and a.kind == "text" and nb == 1024 and bs == (1 << 20))
+        want_legacy = a.legacy if a.legacy is not None else int(a.full and world == 1 and a.mode == "encode" and a.method == "5"
+                                                                 and a.kind == "text" and nb == 1024 and bs == (1 << 20))
         if (want_c1 or want_legacy) and world == 1:
             # the side legs run in child processes with engines of their own: this process is done with the device (max.cfg's
             # 1024 blocks need 235 GiB of model state -- with the headline's 100 GiB still held here the child's budget refuses)
