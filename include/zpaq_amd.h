@@ -147,6 +147,13 @@ int zpq_plan_kernel_kind2(zpq_plan*, int decode, char* note, size_t cap);
 int zpq_plan_kernel_kind3(zpq_plan*, int decode, uint32_t nblocks, char* note, size_t cap);
 /* ... whose longest block has block_bytes bytes (latency shape: 2048-byte steps for blocks of 128 KiB and more) */
 int zpq_plan_kernel_kind4(zpq_plan*, int decode, uint32_t nblocks, uint32_t block_bytes, char* note, size_t cap);
+/* The encoder variant (0 throughput shape, 1 latency shape, 2 latency shape with 2048-byte steps, 3 latency shape with a
+ * wavefront per SIMD) the launch policy (device/launch_policy.hpp) gives every chain of a batch: chain i is blocks[i] blocks of
+ * plans[i], the longest of longest[i] bytes, on a device of `cus` compute units in `xcds` compute dies (XCDs);
+ * persist_expected = the call waits for its results (zpq_*_device with timed = 0 does not).  The knobs of the environment
+ * (ZPAQ_AMD_PIPE_PERSIST / _MODE / _WIDE) count as they do for a batch.  Touches no device. */
+int zpq_encoder_variants(const zpq_plan* const* plans, const uint32_t* blocks, const uint32_t* longest, uint32_t nchains,
+                         int cus, int xcds, int persist_expected, int32_t* variants);
 /* Directories used by the specialisation cache / hipRTC include path. */
 const char* zpq_spec_cache_dir(void);
 const char* zpq_spec_include_dir(void);

@@ -372,7 +372,7 @@ def test_torch_corpus_matches_numpy(gpu):
 def test_device_resident_entry_point_timed_and_in_flight(gpu):
     """zpq_code_device_multi on buffers already in HBM (what bench.py times), in both forms: timed = 1 waits for the results and
     takes the persistent launch; timed = 0 returns with the work in flight on the caller's stream and runs the step kernels --
-    in the shape chosen FOR the step kernels (engine.cpp pipe_mode_for: blocks of 128 KiB and more in a small batch take the
+    in the shape chosen FOR the step kernels (launch_policy.cpp: blocks of 128 KiB and more in a small batch take the
     2048-byte steps).  Same coded bytes either way, and the same as zpq_encode_batch's.  Own process: torch (device buffers)
     has to initialise HIP before the library is loaded."""
     import subprocess

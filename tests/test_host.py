@@ -641,3 +641,38 @@ def test_device_preprocessing_hands_the_buffers_back_as_they_came(zlib_):
     L.zpq_lz77_tokens_host.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     cnt = C.c_size_t(0)
     assert L.zpq_lz77_tokens_host(b"x0,2,12,0,7,21,1", bufs[0].ctypes.data, 1000, None, 16, C.byref(cnt)) != 0
+
+
+def test_encoder_variant_table(zlib_, monkeypatch):
+    """The launch policy (csrc/device/launch_policy.cpp) decides what the code before it decided: every row of
+    tests/golden/encoder_variant_table.json -- recorded from that code, see its "_how" -- through zpq_encoder_variants."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "encoder_variant_table.json")) as fh:
+        table = json.load(fh)
+    plans = {name: zlib_.Plan(bytes.fromhex(h)) for name, h in table["plans"].items()}
+    knobs = sorted({k for env in table["envs"].values() for k in env})
+    assert len(table["rows"]) >= 300
+    seen, demoted, kept, wrong = set(), 0, 0, []
+    alone = {}
+    for env, cus, xcds, persist_expected, chains, want in table["rows"]:
+        for k in knobs + ["ZPAQ_AMD_PIPE_PROFILE", "ZPAQ_AMD_PIPE_TRACE"]:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in table["envs"][env].items():
+            monkeypatch.setenv(k, v)           # (read at every call: the same process sees every environment)
+        got = zlib_.encoder_variants([plans[c[0]] for c in chains], [c[1] for c in chains], [c[2] for c in chains], cus, xcds,
+                                     bool(persist_expected))
+        if got != want:
+            wrong.append((env, cus, xcds, persist_expected, chains, want, got))
+        seen.update(want)
+        if len(chains) == 1:
+            alone[(env, cus, persist_expected, tuple(chains[0]))] = want[0]
+        else:
+            solo = [alone.get((env, cus, persist_expected, tuple(c))) for c in chains]
+            if None not in solo:
+                went = any(s in (1, 3) and w == 0 for s, w in zip(solo, want))
+                demoted += went
+                kept += not went
+    assert not wrong, (len(wrong), wrong[:10])
+    # the table means something: every variant occurs, chains that share the device are demoted in some rows and not in others
+    assert seen == {0, 1, 2, 3}
+    assert demoted >= 1 and kept >= 1, (demoted, kept)

@@ -309,6 +309,16 @@ def builtin_model_header(level: int) -> bytes:
     return h[:hl.value].tobytes()
 
 
+def encoder_variants(plans: Sequence[Plan], blocks: Sequence[int], longest: Sequence[int], cus: int, xcds: int = 8,
+                     persist_expected: bool = True) -> List[int]:
+    """zpq_encoder_variants: the encoder variant the launch policy gives every chain of a batch (no device involved)."""
+    n = len(plans)
+    out = (C.c_int32 * n)()
+    _check(lib().zpq_encoder_variants((C.c_void_p * n)(*[p._h for p in plans]), (C.c_uint32 * n)(*blocks), (C.c_uint32 * n)(*longest),
+                                      C.c_uint32(n), C.c_int(cus), C.c_int(xcds), C.c_int(int(persist_expected)), out))
+    return list(out)
+
+
 def assemble(config: str, args: Optional[Iterable[int]] = None):
     """Compiler: ZPAQL source -> (stored header bytes, pcomp bytes)."""
     a9 = (C.c_int * 9)(*(list(args or []) + [0] * 9)[:9])

@@ -1,10 +1,12 @@
 // C ABI (include/zpaq_amd.h): converts internal Failure exceptions into status
 // codes and implements the batched block-level drop-ins on top of the engine.
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <memory>
 
 #include "device/engine.hpp"
+#include "device/launch_policy.hpp"
 #include "device/plan.hpp"
 #include "device/spec_loader.hpp"
 #include "host/codegen.hpp"
@@ -160,6 +162,21 @@ int zpq_precompile(const zpq_plan* const* plans, size_t n, int decode, int threa
     return done;
   } catch (const Failure& f) { set_last_error(f.what()); return -f.code; }
   catch (const std::exception& ex) { set_last_error(ex.what()); return -ZPQ_E_DEVICE; }
+}
+
+int zpq_encoder_variants(const zpq_plan* const* plans, const uint32_t* blocks, const uint32_t* longest, uint32_t nchains,
+                         int cus, int xcds, int persist_expected, int32_t* variants) {
+  ZPQ_TRY
+  if (!plans || !blocks || !longest || !variants || cus <= 0 || xcds <= 0) fail(ZPQ_E_ARG, "null argument or empty device");
+  std::vector<ChainLoad> chains;
+  for (uint32_t i = 0; i < nchains; ++i) {
+    if (!plans[i]) fail(ZPQ_E_ARG, "null plan");
+    chains.push_back(ChainLoad{plans[i], blocks[i], longest[i]});
+  }
+  const std::vector<int> v = encoder_variants(DeviceShape{cus, xcds}, launch_knobs(), persist_expected != 0, chains);
+  std::copy(v.begin(), v.end(), variants);
+  return ZPQ_OK;
+  ZPQ_CATCH
 }
 
 const uint8_t* zpq_plan_blob(const zpq_plan* p, size_t* len) {

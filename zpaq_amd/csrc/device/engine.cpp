@@ -22,6 +22,7 @@
 
 #include "../host/codegen.hpp"
 #include "kernels.h"
+#include "launch_policy.hpp"
 #include "sa_kernels.h"
 #include "spec_loader.hpp"
 
@@ -87,11 +88,6 @@ struct Event {
   operator hipEvent_t() const { return ev; }
 };
 
-// compute units of the device the batches run on (set when an engine is created; read without the engine's lock by the mode
-// choice and the submission queue: atomic.  Engines on devices of different sizes -- partition modes -- share the figure of
-// the one created last; a residency estimate that is off is caught by the arrival handshake of the persistent launch)
-static std::atomic<int> g_cus_hint{256};
-
 struct Engine {
   std::mutex mu;
   bool ready = false;
@@ -116,7 +112,9 @@ struct Engine {
   bool last_persist = false;           // the last batch's pipelined groups ran as persistent launches
   double last_persist_abort_ms = 0.0;  // ... or: how long it took until a persistent launch of the last batch was given up (0: none was)
   int jit_left = 0;                    // hipRTC compilations still allowed in the current call
-  int cus = 256;                       // compute units of the device
+  std::atomic<int> cus{256};           // compute units of the device (atomic: the submission queue reads the primary engine's without its lock)
+  int xcds = 8;                        // ... and its compute dies
+  DeviceShape shape() const { return DeviceShape{cus.load(), xcds}; }
   hipEvent_t busy = nullptr;           // recorded after the last launch of a call that returned with work in flight
 };
 
@@ -204,7 +202,11 @@ void engine_init_device(Engine& e, int slot, int device) {
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     fail(ZPQ_E_DEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
   e.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  g_cus_hint = e.cus;
+  int xcds = 0;
+  if (hipDeviceGetAttribute(&xcds, hipDeviceAttributeNumberOfXccs, device) != hipSuccess) { (void)hipGetLastError(); xcds = 0; }
+  e.xcds = xcds > 0 ? xcds : 8;
+  if (getenv("ZPAQ_AMD_LOG"))
+    fprintf(stderr, "[zpaq_amd] device %d: %d compute units, %d XCDs%s\n", device, e.cus.load(), e.xcds, xcds > 0 ? "" : " (assumed: the runtime did not say)");
   if (!e.stream) HIP_CHECK(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking));
   // constant tables
   const Tables& t = tables();
@@ -367,77 +369,6 @@ void engine_plan_release(zpq_plan* p) {
 // throughput; below that the 4-block shape (everything in LDS, one workgroup per CU) is faster.
 struct KernelPick { int kind = 0; SpecKernel* spec = nullptr; PipeKernel* pipe = nullptr; int mode = 0; };
 
-// The pipelined encoder has two shapes per chain (host/codegen.hpp PipeOptions): a chain with few blocks in the batch is
-// latency bound -- a step costs one wavefront's serial chain however empty the machine is -- and runs the units with a
-// lane per bit position; a chain that fills the machine is bound by HBM transactions and runs the lane-per-block units,
-// which issue fewer requests.  Measured crossover on the MI355X, -m5 / 1 MiB blocks, 8 hardware queues: latency mode is
-// 1.40 x faster at 64 blocks, 1.07 x at 512, 0.95 x at 768, 0.86 x at 1024 (profiles/r03/call6_summary.txt).
-// ZPAQ_AMD_PIPE_MODE=latency|throughput forces one (A/B, tests).
-static const uint32_t kLatencyModeBlocks = 640;
-static const uint32_t kLongStepBytes = 128u << 10;       // latency shape: blocks this long may take 2048-byte steps (codegen.hpp)
-// ... when what the units of one step pass each other stays small: a step's streams (blocks x 2048 bytes x the chain's
-// ctx / bh / p bytes per input byte) are written and read once within a few steps, and up to ~100 MB of them live in the
-// 256 MB Infinity Cache instead of HBM.  Measured (profiles/r03/call10_summary.txt): -m3's n = 2 chain on 256 blocks
-// (29 MB per step) 483 -> 440 ms; -m5 (588 B per byte) +4 % at 64 blocks (77 MB), +6 % at 512 (616 MB), -20 % at 640.
-static const uint64_t kLongStepStreamBytes = 96ull << 20;
-// Workgroups of a persistent launch of `groups` groups x `wpg` workgroups that one XCD gets (the dispatcher deals a launch's
-// workgroups round-robin over the 8 XCDs; pipe_persist.h maps whole sets of 8 groups one group per XCD, the rest in launch order)
-static uint32_t persist_xcd_share(uint64_t groups, uint64_t wpg) {
-  if (groups >= 8) return (uint32_t)((groups / 8) * wpg + ((groups % 8) * wpg + 7) / 8);
-  return (uint32_t)((groups * wpg + 7) / 8);
-}
-// persist_expected: the call will take the persistent launch if the chain can (it waits for its results: zpq_*_device with timed = 0
-// returns with the work in flight and runs the step kernels) -- the shape is chosen for the launch form that will really run
-static int pipe_mode_for(uint32_t blocks_of_plan, uint32_t longest_block, uint32_t stream_bytes_per_byte, const zpq_plan* plan = nullptr,
-                         bool persist_expected = true) {
-  bool latency = blocks_of_plan <= kLatencyModeBlocks;
-  const char* pp_env = getenv("ZPAQ_AMD_PIPE_PERSIST");
-  bool persist_off = (pp_env && !strcmp(pp_env, "0")) || !persist_expected;
-  // With the persistent launch the shapes differ in how many workgroups a group of blocks needs (-m5: 14 against 8): the
-  // latency shape is the faster one exactly while ALL its workgroups are resident together (measured, profiles/r05
-  // call13: 512 blocks 268 MB/s against 187; beyond that -- 640 blocks: 280 workgroups -- it would need a second round,
-  // which costs a whole block's serial time, and the throughput shape in one round wins: 768 blocks 264 MB/s, 1024: 350)
-  {
-    if (plan && !persist_off) {
-      PipeLayout L1;
-      std::string why;
-      if (pipe_layout(*plan, pipe_options(1), L1, why) && L1.persist_ok) {
-        const uint64_t groups = (blocks_of_plan + (uint32_t)L1.G - 1) / (uint32_t)L1.G;
-        latency = groups * (uint64_t)L1.ps_wpg <= (uint64_t)g_cus_hint.load();
-      } else persist_off = true;       // (a chain that cannot be packed: the step kernels, by round 4's rule)
-    }
-  }
-  if (const char* m = getenv("ZPAQ_AMD_PIPE_MODE")) {
-    if (!strcmp(m, "latency")) latency = true;
-    if (!strcmp(m, "throughput")) latency = false;
-  }
-  if (!latency) return 0;
-  // (long steps exist to spread the per-step launch cost; the persistent launch has none and takes the 512-byte shape)
-  const bool long_steps = persist_off && longest_block >= kLongStepBytes && stream_bytes_per_byte &&
-                          (uint64_t)blocks_of_plan * 2048u * stream_bytes_per_byte <= kLongStepStreamBytes;
-  if (long_steps) return 2;
-  // Variant 3: the latency shape with a wavefront per SIMD (twice the workgroups per group) while THOSE all fit the device
-  // (round 6, call 29: -m5 on 64 / 128 / 256 blocks +17 / +20 / +26 %); a small chain's variant 1 is that shape already.
-  static const bool wide_off = [] { const char* v = getenv("ZPAQ_AMD_PIPE_WIDE"); return v && v[0] == '0'; }();
-  if (plan && !persist_off && !wide_off && !getenv("ZPAQ_AMD_PIPE_MODE")) {
-    PipeLayout L1, L3;
-    std::string why;
-    if (pipe_layout(*plan, pipe_options(1), L1, why) && L1.persist_ok && pipe_layout(*plan, pipe_options(3), L3, why) && L3.persist_ok &&
-        L3.ps_waves < L1.ps_waves) {
-      const uint64_t groups = (blocks_of_plan + (uint32_t)L3.G - 1) / (uint32_t)L3.G;
-      if (groups * (uint64_t)L3.ps_wpg <= (uint64_t)g_cus_hint.load()) return 3;
-    }
-  }
-  return 1;
-}
-// bytes the units of a chain pass each other per input byte (ctx 4, bh 8, p 16 per stream); 0: no pipelined encoder
-static uint32_t pipe_stream_bytes_per_byte(const zpq_plan* plan) {
-  PipeLayout L;
-  std::string why;
-  if (!pipe_layout(*plan, pipe_options(1), L, why)) return 0;
-  return (uint32_t)(L.nctx * 4 + L.nrow * 8 + L.n * 16);
-}
-
 // must_specialise: the plan has blocks of several segments in this batch; only the per-header kernels carry coder and model
 // state across segments, so such a plan compiles whatever the batch's JIT budget says.
 static const bool kAutoTeam = true;     // kernel choice 0 prefers the lockstep decoder for launches that fill the machine
@@ -501,7 +432,8 @@ int engine_plan_kernel_kind(zpq_plan* p, std::string& note, bool decode, uint32_
   require_ready(e);
   bind_device(e);
   e.jit_left = jit_budget();
-  const KernelPick k = kernel_kind(e, p, nblocks > (uint32_t)4 * e.cus, decode, pipe_mode_for(nblocks ? nblocks : 0xFFFFFFFFu, block_bytes, pipe_stream_bytes_per_byte(p), p));
+  const int mode = encoder_variants(e.shape(), launch_knobs(), true, {ChainLoad{p, nblocks ? nblocks : 0xFFFFFFFFu, block_bytes}})[0];
+  const KernelPick k = kernel_kind(e, p, nblocks > (uint32_t)4 * e.cus, decode, mode);
   // (the note of the kernel that was PICKED: the plan's spec_note is the note of whichever shape was loaded last)
   if (k.kind == 3 && k.spec)
     note = k.spec->origin + (k.spec->encode ? "" : (k.spec->threads > 256 ? " (zpq_spec_decode3: row / mixer wavefronts in lockstep)"
@@ -527,10 +459,8 @@ static bool same_group(const LaunchGroup& g, const KernelPick& k, const zpq_plan
 
 // bytes of stream buffer the pipelined encoder needs for `count` blocks of `plan`
 static uint64_t pipe_bytes(const zpq_plan* plan, uint32_t count, int mode) {
-  PipeLayout L;
-  std::string why;
-  if (!pipe_layout(*plan, pipe_options(mode), L, why)) return 0;
-  return (uint64_t)((count + (uint32_t)L.G - 1) / (uint32_t)L.G) * L.group_bytes;
+  const PipeLayout* L = plan_pipe_layout(*plan, mode);
+  return L ? (uint64_t)((count + (uint32_t)L->G - 1) / (uint32_t)L->G) * L->group_bytes : 0;
 }
 
 static hipError_t launch_spec(SpecKernel* k, bool decode, const BlockJob* d_jobs, BlockResult* d_res, uint32_t n,
@@ -619,30 +549,6 @@ struct LateInput {
 // Returns false when the persistent path does not apply (nothing was launched).  A launch whose watchdog fired (a
 // workgroup did not get a compute unit: something else held the GPU) sets *aborted: the caller re-initialises the arenas
 // and runs the six kernels.
-static uint32_t persist_timeout_ticks() {
-  uint32_t ms = 3000;
-  if (const char* t = getenv("ZPAQ_AMD_PERSIST_TIMEOUT_MS")) ms = (uint32_t)std::max(1, atoi(t));
-  return (uint32_t)std::min<uint64_t>((uint64_t)ms * 100000ull, 0xFFFFFFF0ull);      // s_memrealtime: 100 MHz
-}
-
-// ... and how long the workgroups of a launch may wait for each other to become resident (pipe_persist.h pipe_arrived) before the
-// launch is given up untouched: 20 ms without a new arrival (a full grid arrives within microseconds of its first workgroup;
-// measured with 200 of 256 compute units held by another process, profiles/r06: the engine knows ~2 x this after the launch --
-// the workgroups that were left in the queue still have to be dispatched, see the flag and leave)
-static uint32_t persist_arrive_ticks() {
-  uint32_t ms = 20;
-  if (const char* t = getenv("ZPAQ_AMD_PERSIST_ARRIVE_MS")) ms = (uint32_t)std::max(1, atoi(t));
-  return (uint32_t)std::min<uint64_t>((uint64_t)ms * 100000ull, 0xFFFFFFF0ull);
-}
-
-static bool persist_wanted(const std::vector<PipeRun>& runs, bool single_launch_batch) {
-  const char* v = getenv("ZPAQ_AMD_PIPE_PERSIST");
-  if (v && !strcmp(v, "0")) return false;
-  if (getenv("ZPAQ_AMD_PIPE_PROFILE") || getenv("ZPAQ_AMD_PIPE_TRACE")) return false;
-  if (!single_launch_batch) return false;
-  for (const PipeRun& r : runs) if (!r.k->persist || !r.ps_wpg) return false;
-  return !runs.empty();
-}
 
 // workgroups of a run's persistent kernel the device holds at once (0: unknown / none)
 static uint32_t persist_capacity(Engine& e, PipeRun& r) {
@@ -662,30 +568,19 @@ static std::mutex& persist_device_mutex(int device) {
   return mu[(unsigned)device % 64u];
 }
 
-static bool launch_pipe_persist(Engine& e, std::vector<PipeRun>& runs, hipStream_t st, bool* aborted, std::string* what, bool* untouched) {
+static bool launch_pipe_persist(Engine& e, const LaunchKnobs& knobs, std::vector<PipeRun>& runs, hipStream_t st, bool* aborted, std::string* what, bool* untouched) {
   *aborted = false;
   *untouched = false;
   std::lock_guard<std::mutex> device_turn(persist_device_mutex(e.device >= 0 ? e.device : e.slot));
   // what the device holds
-  std::vector<uint32_t> cap(runs.size());
-  for (size_t i = 0; i < runs.size(); ++i) {
-    PipeRun& r = runs[i];
-    cap[i] = persist_capacity(e, r);
-    if (cap[i] < r.ps_wpg) return false;
+  const DeviceShape dev = e.shape();
+  std::vector<PersistRun> need;
+  for (PipeRun& r : runs) {
+    need.push_back(PersistRun{r.ngroups, r.ps_wpg, persist_capacity(e, r)});
+    if (need.back().capacity < r.ps_wpg) return false;
   }
-  // Several runs: only side by side (a second round costs a whole block's serial time whatever it holds).  The dispatcher deals
-  // the workgroups of a launch round-robin over the 8 XCDs and does not look for room elsewhere, so what has to fit is every
-  // XCD's share of every run.  (Measured with the archiver's batch of 14 + 2 groups, calls 24-27: sized against the device as a
-  // whole -- 238 of 256 compute units -- the short run found 2 free compute units per XCD on six XCDs where it needed 3-4,
-  // sat half resident until the long one ended, and the batch took the sum of both: 3.2 s instead of 1.7.)
-  if (runs.size() > 1) {
-    uint32_t share = 0, room = 0xFFFFFFFFu;
-    for (size_t i = 0; i < runs.size(); ++i) {
-      share += persist_xcd_share(runs[i].ngroups, runs[i].ps_wpg);
-      room = std::min(room, cap[i] / 8);
-    }
-    if (share > room) return false;
-  }
+  // Several runs: only side by side (a second round costs a whole block's serial time whatever it holds)
+  if (runs.size() > 1 && !persist_runs_fit(dev, need)) return false;
   // control block per run: [ctl 4 words][group_chunks ngroups][prog ngroups * nunit]
   uint64_t words = 0;
   std::vector<uint64_t> base(runs.size());
@@ -700,7 +595,6 @@ static bool launch_pipe_persist(Engine& e, std::vector<PipeRun>& runs, hipStream
     for (uint32_t g = 0; g < runs[i].ngroups; ++g) host[base[i] + 4 + g] = runs[i].group_chunks[g];
   HIP_CHECK(hipMemcpyAsync(e.pipe_ctl.p, host.data(), words * 4, hipMemcpyHostToDevice, st));
   HIP_CHECK(hipStreamSynchronize(st));            // (host vector; and nothing else of this call may still occupy compute units)
-  const uint32_t timeout = persist_timeout_ticks();
   // ZPAQ_AMD_PERSIST_PROF=<file>: where every unit wavefront's time went (waiting / working, 100 MHz ticks), first run only
   const char* prof_path = getenv("ZPAQ_AMD_PERSIST_PROF");
   unsigned long long* d_prof = nullptr;
@@ -728,10 +622,9 @@ static bool launch_pipe_persist(Engine& e, std::vector<PipeRun>& runs, hipStream
     hipStream_t rs = i == 0 ? st : e.side[i - 1];
     if (i) HIP_CHECK(hipStreamWaitEvent(rs, fork, 0));
     uint32_t* ctl = (uint32_t*)e.pipe_ctl.p + base[i];
-    const uint32_t most = std::max<uint32_t>(1u, cap[i] / r.ps_wpg);                  // groups that are resident together
-    const uint32_t rounds = (r.ngroups + most - 1) / most;
-    const uint32_t per_round = (r.ngroups + rounds - 1) / rounds;                     // (rounds of equal size)
-    rounds_max = std::max(rounds_max, rounds);
+    const PersistRounds pr = persist_rounds(need[i].capacity, r.ps_wpg, r.ngroups);
+    const uint32_t per_round = pr.per_round;                                          // (rounds of equal size)
+    rounds_max = std::max(rounds_max, pr.rounds);
     uint32_t arrived_before = 0;                                                      // workgroups of the run's earlier rounds
     for (uint32_t g0 = 0; g0 < r.ngroups; g0 += per_round) {
       PipeArgs a = r.args;
@@ -741,14 +634,13 @@ static bool launch_pipe_persist(Engine& e, std::vector<PipeRun>& runs, hipStream
       a.prog = ctl + 4 + r.ngroups;
       a.group0 = g0;
       a.ngroups_here = std::min(per_round, r.ngroups - g0);
-      a.timeout_ticks = timeout;
-      a.spread = a.ngroups_here >= 8 ? 8u : 1u;
-      if (const char* v = getenv("ZPAQ_AMD_PERSIST_SPREAD")) a.spread = atoi(v) == 8 ? 8u : 1u;      // (experiments)
+      a.timeout_ticks = persist_ticks(knobs.timeout_ms);      // (the kernels' clock: 100 MHz)
+      a.spread = persist_spread(dev, knobs, a.ngroups_here);
       a.trace = i == prof_run ? d_prof : nullptr;
       const uint32_t grid = a.ngroups_here * r.ps_wpg;
       arrived_before += grid;
       a.arrive_need = arrived_before;
-      a.arrive_ticks = persist_arrive_ticks();
+      a.arrive_ticks = persist_ticks(knobs.arrive_ms);
       void* args[1] = {(void*)&a};
       HIP_CHECK(hipModuleLaunchKernel(r.k->persist, grid, 1, 1, 64u * r.ps_waves, 1, 1, 0, rs, args, nullptr));
     }
@@ -787,9 +679,9 @@ static bool launch_pipe_persist(Engine& e, std::vector<PipeRun>& runs, hipStream
   return true;
 }
 
-static void launch_pipe(Engine& e, std::vector<PipeRun>& runs, hipStream_t st, LateInput* late = nullptr) {
+static void launch_pipe(Engine& e, const LaunchKnobs& knobs, std::vector<PipeRun>& runs, hipStream_t st, LateInput* late = nullptr) {
   if (runs.empty()) { if (late && late->from_byte) (void)late->arrive(); return; }
-  if (getenv("ZPAQ_AMD_PIPE_PROFILE")) {
+  if (knobs.profile) {
     if (late && late->from_byte) HIP_CHECK(hipStreamWaitEvent(st, late->arrive(), 0));
     launch_pipe_profiled(e, runs, st);
     return;
@@ -814,7 +706,7 @@ static void launch_pipe(Engine& e, std::vector<PipeRun>& runs, hipStream_t st, L
   // ZPAQ_AMD_PIPE_TRACE=<file> (with kernels built -DZPQ_TRACE, e.g. ZPAQ_AMD_SPEC_DEFS=-DZPQ_TRACE): one record of four
   // 64-bit words per workgroup and launch -- [kernel << 56 | step << 32 | workgroup], [XCC_ID << 32 | HW_ID], entry and exit
   // on the 100 MHz reference clock -- written to the file when the sequence has finished (profiles/pipe_trace.py)
-  const char* trace_path = getenv("ZPAQ_AMD_PIPE_TRACE");
+  const char* trace_path = knobs.trace ? knobs.trace_path.c_str() : nullptr;
   unsigned long long* d_trace = nullptr;
   uint64_t trace_records = 0;
   std::vector<uint64_t> trace_run_base;                  // first record of each run
@@ -889,7 +781,7 @@ static void launch_pipe(Engine& e, std::vector<PipeRun>& runs, hipStream_t st, L
 // so that each group is one launch (or one launch sequence).
 static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResult* d_res,
                        const std::vector<LaunchGroup>& groups, uint32_t nb, uint64_t max_arena, hipStream_t st,
-                       bool timed, LateInput* late = nullptr, const BlockJob* h_jobs = nullptr,
+                       bool timed, const LaunchKnobs& knobs, LateInput* late = nullptr, const BlockJob* h_jobs = nullptr,
                        const std::function<void()>* before_persist = nullptr) {
   Event ev0(true), ev1(true), ev2(true), ev3(true);
   // enough 256-thread groups per block to stream the arena at HBM rate
@@ -910,9 +802,10 @@ static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResu
   uint64_t pipe_off = 0;
   for (const LaunchGroup& g : groups) {
     if (g.pick.kind != 4) continue;
-    PipeLayout L;
     std::string why;
-    if (!pipe_layout(*g.plan, pipe_options(g.pick.mode), L, why)) fail(ZPQ_E_DEVICE, "pipe layout vanished: " + why);
+    const PipeLayout* layout = plan_pipe_layout(*g.plan, g.pick.mode, &why);
+    if (!layout) fail(ZPQ_E_DEVICE, "pipe layout vanished: " + why);
+    const PipeLayout& L = *layout;
     PipeRun r;
     r.k = g.pick.pipe;
     r.args = PipeArgs{d_jobs + g.first, d_res, g.count, e.d_tables, (uint8_t*)e.pipe.p + pipe_off, 0, 0u};
@@ -983,13 +876,12 @@ static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResu
   // groups are resident together (one round, or rounds that are nearly full: a round costs a block's serial time whatever it holds)
   bool coded = false;
   e.last_persist_abort_ms = 0.0;
-  if (timed && nsingle == 0 && persist_wanted(runs, true)) {
+  bool packable = !runs.empty();
+  for (const PipeRun& r : runs) packable = packable && r.k->persist && r.ps_wpg;
+  if (persist_wanted(knobs, timed && nsingle == 0 && packable)) {
     bool fits = true;
-    if (runs.size() == 1 && persist_capacity(e, runs[0]) >= runs[0].ps_wpg) {
-      const uint32_t per_round = std::max<uint32_t>(1u, persist_capacity(e, runs[0]) / runs[0].ps_wpg);
-      const uint32_t rounds = (runs[0].ngroups + per_round - 1) / per_round;
-      fits = rounds == 1 || (double)runs[0].ngroups / ((double)rounds * per_round) >= 0.85 || getenv("ZPAQ_AMD_PIPE_PERSIST");
-    }
+    if (runs.size() == 1 && persist_capacity(e, runs[0]) >= runs[0].ps_wpg)
+      fits = persist_rounds_worth(knobs, persist_rounds(persist_capacity(e, runs[0]), runs[0].ps_wpg, runs[0].ngroups), runs[0].ngroups);
     if (fits) {
       if (late && late->from_byte) HIP_CHECK(hipStreamWaitEvent(st, late->arrive(), 0));
       // nothing of this call may hold compute units when the grid arrives (the hashing kernel beside the coder, 46 ms for 1024
@@ -999,7 +891,7 @@ static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResu
       bool aborted = false, untouched = false;
       std::string what;
       const auto t_launch = std::chrono::steady_clock::now();
-      if (launch_pipe_persist(e, runs, st, &aborted, &what, &untouched)) {
+      if (launch_pipe_persist(e, knobs, runs, st, &aborted, &what, &untouched)) {
         coded = !aborted;
         if (aborted) {
           e.last_persist_abort_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_launch).count();
@@ -1027,7 +919,7 @@ static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResu
     fprintf(stderr, "[zpaq_amd] pipelined encoder: %zu chain(s)%s -> %s\n", runs.size(), d.c_str(),
             coded ? "one persistent launch each, side by side" : "step kernels");
   }
-  if (!coded) launch_pipe(e, runs, st, late);
+  if (!coded) launch_pipe(e, knobs, runs, st, late);
   for (size_t k = 0; k < nside; ++k) {          // join the side streams back into `st`
     Event done;
     HIP_CHECK(hipEventRecord(done, e.side[k]));
@@ -1069,46 +961,6 @@ static int kind_of_sorted(const std::vector<LaunchGroup>& groups, size_t k) {
 // kernels are compiled side by side on the host cores before the kernels are picked, so that such a batch pays about one
 // compilation time, not one per header.  The code objects land in the cache directory / the loader's in-process store;
 // kernel_kind() then finds them there.
-// blocks of the batch per plan (and the longest of them) -> the variant of its pipelined encoder
-template <class PlanOf, class LenOf>
-static std::map<const zpq_plan*, int> pipe_modes(const std::vector<uint32_t>& order, PlanOf plan_of, LenOf len_of, bool persist_expected = true) {
-  std::map<const zpq_plan*, std::pair<uint32_t, uint32_t>> cnt;
-  for (uint32_t b : order) { auto& c = cnt[plan_of(b)]; ++c.first; c.second = std::max(c.second, (uint32_t)len_of(b)); }
-  std::map<const zpq_plan*, int> mode;
-  for (auto& kv : cnt) mode[kv.first] = pipe_mode_for(kv.second.first, kv.second.second, pipe_stream_bytes_per_byte(kv.first), kv.first, persist_expected);
-  // several chains in one batch share the device's workgroup slots: the persistent launches run side by side only when they
-  // are resident TOGETHER, so chains go from the latency shape to the throughput shape (fewer workgroups per group), the one
-  // that frees the most first, until the batch fits
-  const char* pp = getenv("ZPAQ_AMD_PIPE_PERSIST");
-  // (several chains in one batch: variant 3's workgroups are not part of the arithmetic below -- variant 1 there)
-  if (cnt.size() > 1) for (auto& kv : mode) if (kv.second == 3) kv.second = 1;
-  if (cnt.size() > 1 && !(pp && !strcmp(pp, "0")) && persist_expected && !getenv("ZPAQ_AMD_PIPE_MODE")) {
-    struct Need { const zpq_plan* p; uint64_t lat, thr; };      // what an XCD has to hold of the chain in either shape
-    std::vector<Need> need;
-    bool all = true;
-    for (auto& kv : cnt) {
-      PipeLayout L0, L1;
-      std::string why;
-      if (!pipe_layout(*kv.first, pipe_options(0), L0, why) || !L0.persist_ok || !pipe_layout(*kv.first, pipe_options(1), L1, why) || !L1.persist_ok) { all = false; break; }
-      const uint64_t groups = (kv.second.first + (uint32_t)L0.G - 1) / (uint32_t)L0.G;
-      need.push_back(Need{kv.first, persist_xcd_share(groups, (uint64_t)L1.ps_wpg), persist_xcd_share(groups, (uint64_t)L0.ps_wpg)});
-    }
-    if (all) {
-      for (;;) {
-        uint64_t total = 0;
-        for (const Need& n : need) total += mode[n.p] == 0 ? n.thr : n.lat;
-        if (total <= (uint64_t)g_cus_hint.load() / 8) break;             // (launch_pipe_persist's rule: every XCD's share of every run fits)
-        const Need* best = nullptr;
-        for (const Need& n : need)
-          if (mode[n.p] != 0 && n.lat > n.thr && (!best || n.lat - n.thr > best->lat - best->thr)) best = &n;
-        if (!best) break;
-        mode[best->p] = 0;
-      }
-    }
-  }
-  return mode;
-}
-
 template <class PlanOf>
 static void precompile_unseen(Engine& e, bool decode, bool dense, const std::vector<uint32_t>& order, PlanOf plan_of,
                               const std::map<const zpq_plan*, int>& mode_of) {
@@ -1138,11 +990,18 @@ static void precompile_unseen(Engine& e, bool decode, bool dense, const std::vec
 }
 
 template <class PlanOf, class LenOf>
-static std::vector<LaunchGroup> make_groups(Engine& e, bool decode, std::vector<uint32_t>& order, PlanOf plan_of, LenOf len_of,
+static std::vector<LaunchGroup> make_groups(Engine& e, const LaunchKnobs& knobs, bool decode, std::vector<uint32_t>& order, PlanOf plan_of, LenOf len_of,
                                             const std::set<const zpq_plan*>* multi_segment = nullptr, bool persist_expected = true) {
   const size_t cnt = order.size();
   const bool dense = cnt > (size_t)4 * e.cus;
-  const std::map<const zpq_plan*, int> mode_of = pipe_modes(order, plan_of, len_of, persist_expected);
+  // blocks of the batch per plan (and the longest of them) -> the variant of its pipelined encoder
+  std::map<const zpq_plan*, ChainLoad> load;
+  for (uint32_t b : order) { ChainLoad& c = load[plan_of(b)]; c.plan = plan_of(b); ++c.blocks; c.longest = std::max(c.longest, (uint32_t)len_of(b)); }
+  std::vector<ChainLoad> chains;
+  for (auto& kv : load) chains.push_back(kv.second);
+  const std::vector<int> variants = encoder_variants(e.shape(), knobs, persist_expected, chains);
+  std::map<const zpq_plan*, int> mode_of;
+  for (size_t i = 0; i < chains.size(); ++i) mode_of[chains[i].plan] = variants[i];
   precompile_unseen(e, decode, dense, order, plan_of, mode_of);
   std::vector<KernelPick> pick(cnt);
   for (size_t k = 0; k < cnt; ++k) {
@@ -1244,11 +1103,12 @@ void engine_code_host(bool decode, const std::vector<HostBlock>& blocks, std::ve
       if (now - t0 >= cap) break;
       if (b.approaching == 0 && now - b.last_arrival[d] >= gap) break;
       // a batch that fills the machine already (a bulk zpq_compress_blocks / decode_archive call, or a pool that has queued
-      // that much) gains nothing from company: go at once unless somebody is announced
+      // that much) gains nothing from company: go at once unless somebody is announced.  (No engine is chosen yet: the machine
+      // is the primary engine's, 256 compute units while that one is not initialised.)
       {
         uint64_t queued = 0;
         for (const Ticket* t : b.queue[d]) queued += t->blocks->size();
-        if (b.approaching == 0 && queued >= (uint64_t)4 * (uint64_t)g_cus_hint.load()) break;
+        if (b.approaching == 0 && queued >= (uint64_t)4 * (uint64_t)eng().cus.load()) break;
       }
       b.cv.wait_for(lk, std::chrono::microseconds(500));
     }
@@ -1319,6 +1179,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
   bind_device(e);
   wait_in_flight(e);
   const size_t nb = blocks.size();
+  const LaunchKnobs knobs = launch_knobs();
   e.jit_left = jit_budget();
   results.assign(nb, BlockResult{0, 0, 0, 0});
   size_t pos = 0;
@@ -1361,7 +1222,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
     std::set<const zpq_plan*> multi_segment;
     for (size_t i = pos; i < end; ++i) if (blocks[i].nseg > 1) multi_segment.insert(blocks[i].plan);
     std::vector<LaunchGroup> groups = make_groups(
-        e, decode, order, [&](uint32_t b) { return blocks[b].plan; },
+        e, knobs, decode, order, [&](uint32_t b) { return blocks[b].plan; },
         [&](uint32_t b) { return blocks[b].in_len + blocks[b].prefix_len; }, &multi_segment);
     std::vector<BlockJob> jobs(cnt);
     // inputs are gathered into one buffer and sent with one copy: a page-locked buffer kept by the engine, filled by
@@ -1426,7 +1287,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
     // and copied -- one strided copy -- when the launch loop reaches the first step that may read it (LateInput).
     static const uint32_t kHeadBytes = 64u << 10;
     const uint32_t len0 = cnt ? blocks[order[0]].in_len + blocks[order[0]].prefix_len : 0;
-    bool split = pinned && !decode && cnt >= 64 && len0 >= 8 * kHeadBytes && multi_segment.empty() && !getenv("ZPAQ_AMD_PIPE_PROFILE");
+    bool split = pinned && !decode && cnt >= 64 && len0 >= 8 * kHeadBytes && multi_segment.empty() && !knobs.profile;
     if (const char* sc = getenv("ZPAQ_AMD_SPLIT_COPY")) split = split && sc[0] != '0';      // (A/B aid: "0" = one copy up front)
     for (size_t k = 0; split && k < cnt; ++k)
       split = blocks[order[k]].in_len + blocks[order[k]].prefix_len == len0 && kind_of_sorted(groups, k) == 4;
@@ -1524,7 +1385,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
       if (!shj.empty()) HIP_CHECK(hipStreamWaitEvent(e.stream, sha_done, 0));        // (enqueued above, or by late.arrive() just now)
     };
     launch_all(e, decode, (const BlockJob*)e.jobs.p, (BlockResult*)e.results.p, groups, (uint32_t)cnt, max_arena,
-               e.stream, true, split ? &late : nullptr, jobs.data(), &hashing_done);
+               e.stream, true, knobs, split ? &late : nullptr, jobs.data(), &hashing_done);
     if (split && !tail_sent) HIP_CHECK(hipStreamWaitEvent(e.stream, late.arrive(), 0));   // (no pipelined group after all)
     e.last.init_ms += before.init_ms;
     e.last.code_ms += before.code_ms;
@@ -1613,6 +1474,7 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
   bind_device(e);
   wait_in_flight(e);
   hipStream_t st = stream ? (hipStream_t)stream : e.stream;
+  const LaunchKnobs knobs = launch_knobs();
   e.jit_left = jit_budget();
   auto plan_of = [&](uint32_t b) { return one_plan ? plans[0] : plans[b]; };
   uint64_t need = 0, max_arena = 0;
@@ -1624,7 +1486,7 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
   // group blocks by (kernel, plan); results keep the caller's block order through res_slot
   std::vector<uint32_t> order(nblocks);
   for (uint32_t b = 0; b < nblocks; ++b) order[b] = b;
-  std::vector<LaunchGroup> groups = make_groups(e, decode, order, plan_of, [&](uint32_t b) { return in_len[b]; }, nullptr, timed);
+  std::vector<LaunchGroup> groups = make_groups(e, knobs, decode, order, plan_of, [&](uint32_t b) { return in_len[b]; }, nullptr, timed);
   uint64_t pipe_need = 0;
   for (const LaunchGroup& gr : groups)
     if (gr.pick.kind == 4) pipe_need += pipe_bytes(gr.plan, gr.count, gr.pick.mode);
@@ -1651,7 +1513,7 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
   HIP_CHECK(hipStreamSynchronize(st));   // jobs vector goes out of scope below
   e.last = Timing{};
   e.last_kind = groups.empty() ? 0 : groups[0].pick.kind;
-  launch_all(e, decode, (const BlockJob*)e.jobs.p, d_res, groups, nblocks, max_arena, st, timed, nullptr, jobs.data());
+  launch_all(e, decode, (const BlockJob*)e.jobs.p, d_res, groups, nblocks, max_arena, st, timed, knobs, nullptr, jobs.data());
   if (!timed) mark_in_flight(e, st);
 }
 

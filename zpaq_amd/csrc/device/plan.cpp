@@ -6,11 +6,23 @@
 #include <cmath>
 #include <cstring>
 
+#include "../host/codegen.hpp"
+
 namespace zpq {
 
 static thread_local int tl_plan_device = 0;
 int plan_device_index() { return tl_plan_device; }
 void set_plan_device_index(int dev) { tl_plan_device = (dev >= 0 && dev < zpq_plan::kMaxDevices) ? dev : 0; }
+
+const PipeLayout* plan_pipe_layout(const zpq_plan& plan, int variant, std::string* why_not) {
+  zpq_plan::CachedLayout& c = plan.pipe_layouts[variant];
+  std::call_once(c.once, [&] {
+    auto L = std::make_shared<PipeLayout>();
+    if (pipe_layout(plan, pipe_options(variant), *L, c.why_not)) c.layout = std::move(L);
+  });
+  if (!c.layout && why_not) *why_not = c.why_not;
+  return c.layout.get();
+}
 
 static const int kCompLen[10] = {0, 2, 3, 2, 3, 4, 6, 6, 3, 5};   // libzpaq.cpp:714
 

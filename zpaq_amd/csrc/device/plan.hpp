@@ -1,9 +1,13 @@
 #pragma once
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../host/common.hpp"
 #include "layout.h"
+
+namespace zpq { struct PipeLayout; }
 
 struct zpq_plan {
   std::vector<uint8_t> header;     // stored header bytes
@@ -26,6 +30,10 @@ struct zpq_plan {
     int pipe_state[4] = {0, 0, 0, 0};
     std::string pipe_note, spec_note;     // where the last kernel came from / why it is unavailable
   };
+  // The pipelined encoder's layout per variant (zpq::plan_pipe_layout): a function of the header alone, computed on first
+  // use -- once: engines on several threads share a plan in the sharded path.
+  struct CachedLayout { std::once_flag once; std::shared_ptr<const zpq::PipeLayout> layout; std::string why_not; };
+  mutable CachedLayout pipe_layouts[4];
   static const int kMaxDevices = 16;
   OnDevice dev[kMaxDevices];
   OnDevice& cur();
@@ -40,6 +48,9 @@ int plan_device_index();
 void set_plan_device_index(int dev);
 // Parses a stored block header into a plan; throws Failure(ZPQ_E_HEADER/...).
 zpq_plan* plan_from_header(const U8* header, size_t hlen, bool list_only = false);
+// pipe_layout(plan, pipe_options(variant)) (host/codegen.hpp; the default chunk and group), kept with the plan.
+// nullptr (*why_not says why) when the chain cannot run on the pipelined encoder.
+const PipeLayout* plan_pipe_layout(const zpq_plan& plan, int variant, std::string* why_not = nullptr);
 }
 
 inline zpq_plan::OnDevice& zpq_plan::cur() { return dev[zpq::plan_device_index()]; }

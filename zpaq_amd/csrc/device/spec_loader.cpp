@@ -457,11 +457,7 @@ PipeKernel* pipe_kernel_for(zpq_plan* plan, int mode, bool allow_jit, bool* did_
     return nullptr;
   }
   if (hipModuleGetFunction(&k->persist, k->module, "zpq_pipe_persist") != hipSuccess) { (void)hipGetLastError(); k->persist = nullptr; }
-  {
-    PipeLayout PL;
-    std::string why2;
-    if (pipe_layout(*plan, pipe_options(mode), PL, why2)) for (int v : PL.mix_packed) k->any_packed = k->any_packed || v != 0;
-  }
+  if (const PipeLayout* PL = plan_pipe_layout(*plan, mode)) for (int v : PL->mix_packed) k->any_packed = k->any_packed || v != 0;
   k->origin = origin;
   plan->cur().pipe[mode] = k;
   plan->cur().pipe_state[mode] = 1;

@@ -44,7 +44,7 @@ struct PipeOptions {
 // whatever it holds; a batch that fills the GPU hides that behind 2 ms of work, a small one does not (-m5 on 64 blocks:
 // 0.98 ms per 512-byte step against 0.65 ms for the longest chain), so blocks long enough to fill a long pipeline
 // (128 KiB and more: 16 levels x 2048 bytes of fill) take four times fewer, four times longer steps -- as long as the
-// streams of one step stay cache-sized (engine.cpp::pipe_mode_for has the rule and the measurements).  3 = latency shape with
+// streams of one step stay cache-sized (device/launch_policy.cpp has the rule and the measurements).  3 = latency shape with
 // a wavefront per SIMD (workgroups of 4 wavefronts: twice the workgroups per group), taken by the persistent launch while those
 // all fit the device (round 6; a chain of up to 32 unit wavefronts has that shape as its variant 1 already).
 static const int kPipeVariants = 4;
