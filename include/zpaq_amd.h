@@ -236,6 +236,10 @@ int zpq_sha1_batch_device(const uint8_t* const* in, const uint32_t* len, uint32_
  * (staging + H2D + kernels + D2H), [3] archive stitching, [4] / [5] the Predictor-init and coding kernels inside
  * [2] (hipEvents), [6] blocks. */
 int zpq_last_api_timing(double out[8]);
+/* Blocks of this process's last zpq_compress_blocks call whose LZ77 parse through LZBuffer's hash table (method 1, method 2
+ * below type 64, x / s methods with args[5] - args[0] < 21) ran on the device (device/lz77_hash_kernel.h); 0 when the host
+ * parsed them (a small batch, ZPAQ_AMD_DEVICE_PARSE=0, parameters outside the device's range, no device). */
+uint32_t zpq_last_hash_parse_blocks(void);
 /* Runs a tiny kernel exercising the cross-lane idioms (DPP reduction, readlane,
  * bpermute); out8[0..5] must equal {2016, 21344, 123, 2016, 133, 13671}. */
 int zpq_selftest(int32_t out8[8]);
@@ -300,8 +304,10 @@ int zpq_preprocess_block_sa(const char* xmethod, uint8_t* data, uint32_t n, cons
 /* The pre-processors behind the sort for n buffers in one device call: the suffix sort, the LZ77 parse (LZBuffer::fill with a
    suffix array, libzpaq.cpp:6693-6757) and the BWT's last column run on the GPU (device/lz77_kernel.h), the parse comes back
    as a list of matches (4 x uint32: position of the search, offset, length, literals in front) and the host writes LZBuffer's
-   codes from it (6759-6883).  zpq_preprocess_blocks_device returns what zpq_preprocess_block does, buffer by buffer;
-   zpq_lz77_tokens_host is the host's list, zpq_lz77_serialize the coder. */
+   codes from it (6759-6883).  Methods whose LZ77 searches the hash table instead (args[5] - args[0] < 21; 6702-6782) are
+   parsed by device/lz77_hash_kernel.h the same way, without a sort of suffixes.  zpq_preprocess_blocks_device returns what
+   zpq_preprocess_block does, buffer by buffer; zpq_lz77_tokens_host is the host's list (either search), zpq_lz77_serialize
+   the coder. */
 int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                                  size_t* outlen);
 int zpq_lz77_tokens_host(const char* xmethod, uint8_t* data, uint32_t n, uint32_t* tokens4, size_t cap, size_t* count);

@@ -78,6 +78,8 @@ def lib():
                                     C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                     C.c_void_p, C.c_void_p, C.c_int]
     L.zpq_decode_device.argtypes = L.zpq_encode_device.argtypes
+    L.zpq_last_hash_parse_blocks.restype = C.c_uint32
+    L.zpq_last_hash_parse_blocks.argtypes = []
     _lib = L
     return L
 
@@ -249,6 +251,11 @@ def compress_blocks(blocks: Sequence, method: str, filenames: Optional[Sequence[
                                        OA, OC, OL)
     _check(rc)
     return [outs[i][:OL[i]].tobytes() for i in range(n)]
+
+
+def last_hash_parse_blocks() -> int:
+    """Blocks of the last compress_blocks call whose hash-table LZ77 parse (method 1, ...) ran on the device."""
+    return int(lib().zpq_last_hash_parse_blocks())
 
 
 def compress_block(data, method: str, filename: Optional[str] = None, comment: Optional[str] = None,

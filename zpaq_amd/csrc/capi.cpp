@@ -473,12 +473,12 @@ int zpq_preprocess_block_sa(const char* xmethod, uint8_t* data, uint32_t n, cons
   ZPQ_CATCH
 }
 
-// ---- the LZ77 parse through a suffix array as a token list (host/common.hpp LzToken: i, off, len, blit) ----
+// ---- the LZ77 parse (through a suffix array or LZBuffer's hash table) as a token list (host/common.hpp LzToken: i, off, len, blit) ----
 static void lz_args(const char* xmethod, int args[9]) {
   if (!xmethod) fail(ZPQ_E_ARG, "null argument");
   (void)make_config(xmethod, args);
   const int level = args[1] & 3;
-  if (args[1] < 1 || args[1] > 7 || level < 1 || level > 2 || args[5] - args[0] < 21) fail(ZPQ_E_ARG, "not an LZ77 method that searches a suffix array");
+  if (args[1] < 1 || args[1] > 7 || level < 1 || level > 2) fail(ZPQ_E_ARG, "not an LZ77 method");
 }
 
 // The host's parse of one block (data is E8E9-filtered in place first when the method says so).
@@ -514,14 +514,16 @@ int zpq_lz77_serialize(const char* xmethod, const uint8_t* data, uint32_t n, con
 }
 
 // What zpq_preprocess_block makes, for n host buffers in one call with the sort, the LZ77 parse and the BWT on the device
-// (device/sa_kernels.hip, device/lz77_kernel.h); only for methods whose pre-processor sorts.  E8E9 is applied in place.
+// (device/sa_kernels.hip, device/lz77_kernel.h), or the LZ77 parse through the hash table (device/lz77_hash_kernel.h); only for
+// methods whose pre-processor sorts or is such an LZ77.  E8E9 is applied in place.
 int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                                  size_t* outlen) {
   ZPQ_TRY
   if (!xmethod || (n && (!data || !len || !out || !cap || !outlen))) fail(ZPQ_E_ARG, "null argument");
   int args[9];
   (void)make_config(xmethod, args);
-  if (!preprocess_needs_suffix_array(args)) fail(ZPQ_E_ARG, "the method's pre-processor does not sort");
+  const bool hashed = preprocess_is_hash_lz77(args);
+  if (!hashed && !preprocess_needs_suffix_array(args)) fail(ZPQ_E_ARG, "the method's pre-processor neither sorts nor parses");
   // E8E9 rewrites the caller's buffers in place (as the reference rewrites its input).  They keep the filter only when the call
   // succeeds: on EVERY failure exit -- the device declines, something throws between the first filtered buffer and the last
   // copied output, an output buffer is too small -- the buffers filtered so far go back as they came, so that a caller
@@ -533,11 +535,11 @@ int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, cons
   std::vector<SortJob> jobs;
   for (uint32_t i = 0; i < n; ++i) {
     if (args[1] > 4) { e8e9_forward(data[i], len[i]); guard.done = i + 1; }
-    jobs.push_back(sort_job(data[i], len[i], args));
+    jobs.push_back(hashed ? hash_job(data[i], len[i], args) : sort_job(data[i], len[i], args));
   }
   std::vector<SortOut> outs;
   std::string note;
-  if (!engine_sort_preprocess(jobs, outs, note)) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
+  if (!(hashed ? engine_hash_preprocess(jobs, outs, note) : engine_sort_preprocess(jobs, outs, note))) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
   std::vector<std::vector<U8>> pres(n);
   bool fits = true;
   for (uint32_t i = 0; i < n; ++i) {
@@ -571,6 +573,8 @@ int zpq_last_api_timing(double out[8]) {
   out[4] = t.kernel_init_ms; out[5] = t.kernel_code_ms; out[6] = (double)t.blocks; out[7] = (double)t.sa_device_blocks;
   return ZPQ_OK;
 }
+
+uint32_t zpq_last_hash_parse_blocks(void) { return last_api_timing().hash_parse_blocks; }
 
 size_t zpq_table(int which, void* out, size_t cap) {
   try {

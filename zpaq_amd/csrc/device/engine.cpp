@@ -1766,6 +1766,71 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   return true;
 }
 
+bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note) {
+  const size_t n = jobs.size();
+  out.assign(n, SortOut());
+  uint64_t total = 0, ntok = 0, nkeys = 0, nidx = 0;
+  std::vector<LzBlock> blk(n);
+  for (size_t i = 0; i < n; ++i) {
+    const SortJob& j = jobs[i];
+    if (!hash_job_in_range(j)) { note = "LZ77 parameters or block size outside the device hash parser's range"; return false; }
+    LzBlock& B = blk[i];
+    memset(&B, 0, sizeof(B));
+    B.off = total;
+    B.n = j.n;
+    B.kind = j.n ? j.kind : 0u;
+    B.min_match = j.min_match; B.lookahead = j.lookahead; B.bucket = j.bucket; B.checkbits = j.checkbits;
+    B.min_match2 = j.min_match2; B.ht_bits = j.ht_bits;
+    B.tok_off = ntok;
+    B.tok_cap = j.n / j.min_match + 2;
+    ntok += B.tok_cap;
+    lz_hash_plan(B, nkeys, nidx);
+    total += j.n;
+  }
+  if (!total) return true;
+  if (n > 65535 || total >= (1ull << 31)) { note = "batch outside the device hash parser's range"; return false; }
+  Engine& e = eng();
+  std::lock_guard<std::mutex> g(e.mu);
+  require_ready(e);
+  bind_device(e);
+  wait_in_flight(e);
+  const size_t ws = lzh_workspace_bytes(total, nkeys, nidx);
+  const uint64_t in_bytes = (total + 255) & ~255ull;
+  // io_out: decisions (16 B per element), tokens, counts, the block table
+  const uint64_t o_tok = 16 * total;
+  const uint64_t o_cnt = (o_tok + 16 * ntok + 255) & ~255ull;
+  const uint64_t o_blk = (o_cnt + 4 * n + 255) & ~255ull;
+  const uint64_t out_bytes = o_blk + n * sizeof(LzBlock) + 256;
+  if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "hash parse workspace exceeds the device budget"; return false; }
+  e.io_in.ensure(in_bytes + 64);
+  e.io_out.ensure(out_bytes);
+  e.arena.ensure(ws);
+  const bool pinned = in_bytes >= (1u << 20) && e.pin_in.ensure(in_bytes + 64);
+  std::unique_ptr<uint8_t[]> pageable;
+  uint8_t* stage = pinned ? (uint8_t*)e.pin_in.p : (pageable.reset(new uint8_t[in_bytes + 64]), pageable.get());
+  for (size_t i = 0; i < n; ++i)
+    if (jobs[i].n) memcpy(stage + blk[i].off, jobs[i].data, jobs[i].n);
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage, total, hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 4 * n, e.stream));
+  const hipError_t rc = launch_hash_parse((const uint8_t*)e.io_in.p, (const LzBlock*)(ob + o_blk), (uint32_t)n, total, nkeys, nidx, e.arena.p, e.arena.cap,
+                                          ob, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), e.stream);
+  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device hash parse failed: ") + hipGetErrorString(rc); return false; }
+  std::vector<uint32_t> cnt(n);
+  HIP_CHECK(hipMemcpyAsync(cnt.data(), ob + o_cnt, 4 * n, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t i = 0; i < n; ++i) {
+    const LzBlock& B = blk[i];
+    if (cnt[i] > B.tok_cap) { note = "LZ77 token list overflowed"; return false; }
+    out[i].toks.resize(cnt[i]);
+    if (cnt[i]) HIP_CHECK(hipMemcpyAsync(out[i].toks.data(), ob + o_tok + 16 * B.tok_off, 16ull * cnt[i], hipMemcpyDeviceToHost, e.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  note = "device, " + std::to_string(nkeys) + " keys";
+  return true;
+}
+
 int engine_jit_threads() { return jit_threads(); }
 
 int engine_selftest(int32_t out[8]) {

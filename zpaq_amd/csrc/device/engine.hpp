@@ -73,7 +73,7 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
 // The pre-processors behind the sort for a whole batch on the device (device/lz77_kernel.h): blocks of kind 1 / 2 come back as
 // the LZ77 parse's list of matches (host/preproc.cpp lz77_serialize codes it), blocks of kind 3 as the BWT stream
 // preprocess_block would make (n + 5 bytes).  false + note when the device declines (then the host does it all).
-struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; };
+struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0; };   // (the last two: hash_job)
 struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; };
 bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note);
 // the job of a block whose method has these args (LZBuffer's parameters: libzpaq.cpp:6647-6692)
@@ -81,6 +81,25 @@ inline SortJob sort_job(const U8* data, U32 n, const int args[9]) {
   const U32 level = (U32)(args[1] & 3);
   if (level == 3) return SortJob{data, n, 3u, 0u, 0u, 0u, 0u};
   return SortJob{data, n, level, (U32)args[2], (U32)args[6], args[4] >= 0 && args[4] < 31 ? (1u << args[4]) - 1u : 0x7FFFFFFFu, (U32)(17 + args[0])};
+}
+// The LZ77 parse through LZBuffer's hash table (args[5] - args[0] < 21: method 1, method 2 below type 64, ...) for a whole batch on
+// the device (device/lz77_hash_kernel.h): every block comes back as its list of matches, like the kind 1 / 2 blocks of
+// engine_sort_preprocess.  Same buffers, same contract: false + note when the device declines or fails (then the host parses),
+// nothing of the caller's is touched.
+bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note);
+inline SortJob hash_job(const U8* data, U32 n, const int args[9]) {
+  SortJob j{data, n, (U32)(args[1] & 3), (U32)args[2], (U32)args[6], args[4] >= 0 && args[4] < 31 ? (1u << args[4]) - 1u : 0x7FFFFFFFu, (U32)(12 - args[0])};
+  j.min_match2 = (U32)args[3];
+  j.ht_bits = (U32)args[5];
+  return j;
+}
+// What the device's hash-table parser takes (everything else stays on the host): blocks below 2^24 bytes, tables of up to 2^24
+// slots that hold a whole bucket, a look-ahead the decision word has room for, and min_match >= 2 -- with 1 the reference
+// compares the byte in front of a candidate, which for position 0 lies outside the block.  Level 2 with min_match > 64 searches
+// nothing in the reference.
+inline bool hash_job_in_range(const SortJob& j) {
+  return (j.kind == 1 || j.kind == 2) && j.n < (1u << 24) && j.ht_bits >= 1 && j.ht_bits <= 24 && j.bucket < (1u << j.ht_bits) && j.lookahead <= 255 &&
+         j.min_match >= 2 && j.min_match <= 255 && j.min_match2 <= 255 && (j.kind == 1 || j.min_match <= 64) && j.checkbits >= 1 && j.checkbits <= 12;
 }
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)

@@ -191,9 +191,34 @@ struct LzBlock {            // one per block of the batch
   uint32_t tok_cap;
   uint32_t kind;            // 1 / 2: LZ77 with bit-packed / byte-aligned codes; 3: BWT; 0: nothing to do here
   uint32_t min_match, lookahead, bucket, checkbits;     // LZBuffer's parameters (args[2], args[6], 2^args[4] - 1, 17 + args[0])
+  // the hash-table search (device/lz77_hash_kernel.h); ht_bits == 0: the block is searched through its suffix array
+  uint32_t ht_bits;         // args[5]: the table has 2^ht_bits slots (checkbits is 12 - args[0] then)
+  uint32_t min_match2;      // args[3]: length of the longer context, 0 = none
+  uint32_t idx_bits;        // its index has 2^idx_bits + 1 entries: where the keys of each slot prefix start
+  uint32_t nkeys;           // keys of the block: ins_end x (1 or 2)
+  uint32_t ins_end;         // positions below max(0, n - minMatchBoth) are inserted, the hashes stand still from there on
   uint32_t pad;
+  uint64_t key_off;         // its first key in the batch's key array
+  uint64_t idx_off;         // its first entry in the batch's index array
 };
 struct LzTok { uint32_t i, off, len, blit; };            // = host/common.hpp LzToken
+// The derived fields of a hash-table block (n, min_match, min_match2, lookahead, bucket, ht_bits set; bucket < 2^ht_bits): what
+// is inserted, and an index that resolves slot prefixes down to about 8 keys each -- never finer than a bucket, because the slots
+// one search reads (h ^ k, k <= bucket) must share their prefix.  nkeys / nidx: running sums over the batch.
+static inline void lz_hash_plan(LzBlock& B, uint64_t& nkeys, uint64_t& nidx) {
+  const uint32_t ctx2 = B.min_match2 + B.lookahead, both = (B.min_match > ctx2 ? B.min_match : ctx2) + 4u;
+  B.ins_end = B.n > both ? B.n - both : 0u;
+  B.nkeys = B.ins_end * (B.min_match2 ? 2u : 1u);
+  uint32_t bucket_bits = 0, want = 0;
+  while ((1u << bucket_bits) <= B.bucket) ++bucket_bits;
+  while (want < 24u && (8ull << want) < B.nkeys) ++want;
+  const uint32_t most = B.ht_bits > bucket_bits ? B.ht_bits - bucket_bits : 0u;
+  B.idx_bits = want < most ? want : most;
+  B.key_off = nkeys;
+  B.idx_off = nidx;
+  nkeys += B.nkeys;
+  nidx += (1ull << B.idx_bits) + 1u;
+}
 
 // Cap on HCOMP instructions per input byte: the reference has no limit (a
 // hostile header can loop forever); a device kernel must not hang.

@@ -24,4 +24,11 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
 hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_all, const SaSideArrays& side, const LzBlock* blocks, uint32_t nblocks,
                                      uint64_t total, bool any_lz, bool any_bwt, void* res, LzTok* toks, uint32_t* counts, uint8_t* bwt_out,
                                      uint32_t* bwt_idx, hipStream_t st);
+// The LZ77 parse through LZBuffer's hash table for a batch (device/lz77_hash_kernel.h): keys, one radix sort, the index of slot
+// prefixes, the search (16 bytes of decisions per element in `res`), then lz77_walk_kernel as behind the sort.  The caller fills
+// blocks[b].ht_bits / min_match2 / ins_end / nkeys / key_off / idx_bits / idx_off; nkeys, nidx: the sums of the blocks' keys and
+// index entries (2^idx_bits + 1 each).  ws: lzh_workspace_bytes(total, nkeys, nidx) bytes of device memory.
+size_t lzh_workspace_bytes(uint64_t total, uint64_t nkeys, uint64_t nidx);
+hipError_t launch_hash_parse(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, uint64_t nkeys, uint64_t nidx, void* ws,
+                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st);
 }  // namespace zpq

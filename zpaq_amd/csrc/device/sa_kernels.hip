@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
 #include "sa_kernels.h"
 
@@ -88,6 +89,20 @@ __global__ __launch_bounds__(256) void bwt_emit_kernel(const uint8_t* in_all, co
                                                        uint64_t total, uint8_t* out_all, uint32_t* idx) {
   bwt_emit_body(in_all, sa_all, blk, blocks, total, out_all, idx);
 }
+
+__global__ __launch_bounds__(256) void lzh_keys_kernel(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, uint16_t* blk,
+                                                       uint64_t* keys) {
+  lzh_keys_body(in_all, blocks, nblocks, total, blk, keys);
+}
+__global__ __launch_bounds__(256) void lzh_index_kernel(const uint64_t* keys, uint64_t nkeys, const LzBlock* blocks, uint32_t* idx) {
+  lzh_index_body(keys, nkeys, blocks, idx);
+}
+__global__ __launch_bounds__(256) void lzh_search_kernel(const uint8_t* in_all, const uint64_t* keys, const uint32_t* idx, const uint16_t* blk,
+                                                         const LzBlock* blocks, uint64_t total, uint4* res) {
+  lzh_search_body(in_all, keys, idx, blk, blocks, total, res);
+}
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -160,6 +175,41 @@ hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_a
   }
   if (any_bwt)
     hipLaunchKernelGGL(bwt_emit_kernel, dim3(g), dim3(256), 0, st, in_all, sa_all, (const uint16_t*)side.blk, blocks, total, bwt_out, bwt_idx);
+  return hipGetLastError();
+}
+
+size_t lzh_workspace_bytes(uint64_t total, uint64_t nkeys, uint64_t nidx) {
+  size_t sort_tmp = 0;
+  if (nkeys) (void)rocprim::radix_sort_keys(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)nkeys, 0, 64);
+  // keys x 2, the element -> block map, the index, library scratch
+  return 2 * up256((size_t)nkeys * 8) + up256((size_t)total * 2) + up256((size_t)nidx * 4) + up256(sort_tmp) + 4096;
+}
+
+// The LZ77 parse through the hash table for a whole batch (device/lz77_hash_kernel.h): blocks[b] with ht_bits != 0, key_off /
+// idx_off / nkeys / ins_end / idx_bits filled in by the caller (nkeys, nidx: the sums over the batch).
+hipError_t launch_hash_parse(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, uint64_t nkeys, uint64_t nidx, void* ws,
+                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st) {
+  if (!total || !nblocks) return hipSuccess;
+  if (nblocks > 65535u || total >= (1ull << 32) || ws_bytes < lzh_workspace_bytes(total, nkeys, nidx)) return hipErrorInvalidValue;
+  uint8_t* p = (uint8_t*)ws;
+  uint64_t* keys = (uint64_t*)p; p += up256((size_t)nkeys * 8);
+  uint64_t* keys2 = (uint64_t*)p; p += up256((size_t)nkeys * 8);
+  uint16_t* blk = (uint16_t*)p; p += up256((size_t)total * 2);
+  uint32_t* idx = (uint32_t*)p; p += up256((size_t)nidx * 4);
+  void* tmp = p;
+  const size_t tmp_bytes = ws_bytes - (size_t)(p - (uint8_t*)ws);
+  hipLaunchKernelGGL(lzh_keys_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, blocks, nblocks, total, blk, keys);
+  if (nkeys) {
+    unsigned blk_bits = 1;
+    while ((1u << blk_bits) < nblocks) ++blk_bits;
+    size_t need = tmp_bytes;
+    const hipError_t e = rocprim::radix_sort_keys(tmp, need, keys, keys2, (size_t)nkeys, 0, 48 + blk_bits, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lzh_index_kernel, dim3(grid_for(nkeys)), dim3(256), 0, st, (const uint64_t*)keys2, nkeys, blocks, idx);
+  }
+  hipLaunchKernelGGL(lzh_search_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, (const uint64_t*)keys2, (const uint32_t*)idx,
+                     (const uint16_t*)blk, blocks, total, (uint4*)res);
+  hipLaunchKernelGGL(lz77_walk_kernel, dim3(nblocks), dim3(64), 0, st, blocks, (const uint4*)res, toks, counts);
   return hipGetLastError();
 }
 

@@ -193,6 +193,10 @@ void parallel_blocks(size_t n, F&& fn) {
 
 }  // namespace
 
+// From what batch on the hash-table LZ77 parse goes to the device (DESIGN 4.5 has the measurements behind it)
+static const size_t kHashParseMinBlocks = 4;
+static const U64 kHashParseMinBytes = 1u << 20;
+
 void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool dosha1,
                      std::vector<std::vector<U8>>& archives) {
   const size_t nb = in.size();
@@ -220,7 +224,7 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     ~Announce() { off(); }
   } announce;
   // 1. host front half, parallel over blocks: method -> chain; then the pre-processor; then the archive's front
-  struct Front { int args[9]; Assembled as; bool sorts = false; };
+  struct Front { int args[9]; Assembled as; bool sorts = false, hashes = false; };
   std::vector<Front> front(nb);
   parallel_blocks(nb, [&](size_t b) {
     Work& w = work[b];
@@ -236,6 +240,7 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     if (dosha1 && !w.sha1_on_device) { Sha1 s; s.update(in[b].data, n); memcpy(w.sha1, s.result(), 20); }
     if ((U64)n + 4096 > (0x100000ull << f.args[0])) fail(ZPQ_E_ARG, "block larger than the method's block size");
     f.sorts = n > 0 && preprocess_needs_suffix_array(f.args);
+    f.hashes = n > 0 && preprocess_is_hash_lz77(f.args);
   });
   // Blocks whose pre-processor sorts suffixes (byte-aligned LZ77 with a suffix array: level 3; BWT): one suffix sort for
   // all of them on the device when there are enough to fill it (device/sa_kernels.hip), the host's SA-IS per block otherwise
@@ -282,6 +287,37 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
       tm.sa_device_blocks = got ? (U32)sorting.size() : 0;
     } else {
       for (size_t b : sorting) front[b].sorts = false;   // nothing was done up front: preprocess_block does it all
+    }
+  }
+  // Blocks whose LZ77 searches LZBuffer's hash table (method 1, method 2 below type 64, the "barely compressible" branches of 3
+  // and 4, x / s methods with args[5] - args[0] < 21): parsed on the device as well when there are enough of them
+  // (device/lz77_hash_kernel.h: what a slot holds when a position is searched does not depend on the parse); the list
+  // of matches comes back and the host writes the codes, as behind the sort.  Outside the device's range (hash_job_in_range),
+  // with ZPAQ_AMD_DEVICE_PARSE=0, or when the device declines or fails, preprocess_block parses on the host -- E8E9 already
+  // applied in the last case.
+  {
+    std::vector<size_t> hashing;
+    U64 hash_bytes = 0;
+    for (size_t b = 0; b < nb; ++b) if (front[b].hashes) { hashing.push_back(b); hash_bytes += in[b].n; }
+    bool in_range = hashing.size() <= 65535 && hash_bytes < (1ull << 31);
+    for (size_t b : hashing) in_range = in_range && hash_job_in_range(hash_job(in[b].data, in[b].n, front[b].args));
+    const char* knob = getenv("ZPAQ_AMD_DEVICE_PARSE");
+    if (in_range && (!knob || knob[0] != '0') && hashing.size() >= kHashParseMinBlocks && hash_bytes >= kHashParseMinBytes &&
+        engine_device_count() > 0) {
+      parallel_blocks(hashing.size(), [&](size_t k) {
+        const size_t b = hashing[k];
+        if (front[b].args[1] > 4) e8e9_forward(in[b].data, in[b].n);
+      });
+      std::vector<SortJob> hj;
+      for (size_t b : hashing) hj.push_back(hash_job(in[b].data, in[b].n, front[b].args));
+      std::vector<SortOut> ho;
+      std::string note;
+      bool got = false;
+      try { got = engine_hash_preprocess(hj, ho, note); } catch (const Failure&) { got = false; }      // (any device trouble: the host parses)
+      if (got)
+        for (size_t k = 0; k < hashing.size(); ++k) { dev_pre[hashing[k]] = std::move(ho[k]); have_pre[hashing[k]] = 1; }
+      for (size_t b : hashing) front[b].sorts = true;                 // (E8E9 is done either way)
+      tm.hash_parse_blocks = got ? (U32)hashing.size() : 0;
     }
   }
   parallel_blocks(nb, [&](size_t b) {

@@ -93,6 +93,8 @@ std::vector<U32> suffix_array(const U8* in, U32 n);
 bool preprocess_block(U8* data, U32 n, const int args[9], std::vector<U8>& out, const U32* sa = nullptr, bool e8e9_done = false);
 // does this method's pre-processor sort the block's suffixes (BWT, or LZ77 searching through a suffix array)?
 bool preprocess_needs_suffix_array(const int args[9]);
+// the pre-processor is LZ77 through LZBuffer's hash table (levels 1 / 2 with args[5] - args[0] < 21: method 1, method 2 below type 64, ...)
+bool preprocess_is_hash_lz77(const int args[9]);
 // The LZ77 parse through a suffix array as a list of matches, in order: the search stood at `i`, `blit` literals in front of
 // the match belong to it (a look-ahead match), then `len` bytes from `off` back.  Every position the list does not cover is
 // a literal.  lz77_host_tokens: the host's parse; lz77_serialize: the coded stream (LZBuffer's byte-aligned or bit-packed

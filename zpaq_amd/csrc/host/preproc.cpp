@@ -474,6 +474,13 @@ bool preprocess_needs_suffix_array(const int args[9]) {
   return level == 3 || ((level == 1 || level == 2) && args[5] - args[0] >= 21);
 }
 
+bool preprocess_is_hash_lz77(const int args[9]) {
+  const int kind = args[1];
+  if (kind < 1 || kind > 7 || kind == 4) return false;
+  const int level = kind & 3;
+  return (level == 1 || level == 2) && args[5] - args[0] < 21;
+}
+
 bool preprocess_block(U8* data, U32 n, const int args[9], std::vector<U8>& out, const U32* sa_in, bool e8e9_done) {
   out.clear();
   const int kind = args[1];
@@ -507,7 +514,7 @@ bool preprocess_block(U8* data, U32 n, const int args[9], std::vector<U8>& out, 
 
 void lz77_host_tokens(const U8* data, U32 n, const int args[9], const U32* sa, std::vector<LzToken>& toks) {
   toks.clear();
-  if ((args[1] & 3) < 1 || (args[1] & 3) > 2 || args[5] - args[0] < 21) fail(ZPQ_E_ARG, "not an LZ77 method that searches a suffix array");
+  if ((args[1] & 3) < 1 || (args[1] & 3) > 2) fail(ZPQ_E_ARG, "not an LZ77 method");
   std::vector<U8> unused;
   Lz77 lz(data, n, args, unused, sa);
   lz.tokens(toks);
