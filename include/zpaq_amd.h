@@ -240,6 +240,16 @@ int zpq_last_api_timing(double out[8]);
  * below type 64, x / s methods with args[5] - args[0] < 21) ran on the device (device/lz77_hash_kernel.h); 0 when the host
  * parsed them (a small batch, ZPAQ_AMD_DEVICE_PARSE=0, parameters outside the device's range, no device). */
 uint32_t zpq_last_hash_parse_blocks(void);
+/* Blocks of this process's last zpq_compress_blocks call whose LZ77 stream (LZBuffer's codes, libzpaq.cpp:6759-6883) was written
+ * on the device from the list of matches the device's parse left there (device/lz77_codes_kernel.h): the finished stream came
+ * back over PCIe instead of 16 bytes per match, and no host core walked the block again.  0 when the host wrote the codes: the
+ * host parsed (see above), ZPAQ_AMD_DEVICE_CODES=0, or a batch for which it does not pay.
+ *   ZPAQ_AMD_DEVICE_CODES=0|1: 0 keeps the download of the list and the host's coder (host/preproc.cpp lz77_serialize), 1 writes
+ *   every such batch's codes on the device.  Unset, the engine decides per batch once the sizes are known: on the device when
+ *   the streams are smaller than the lists (16 bytes per match) and not below 1 % of the input -- an incompressible batch has no
+ *   matches, its list is empty and its stream is the input, so it stays with the host (measured: DESIGN 4.5.2).
+ *   ZPAQ_AMD_DEVICE_PARSE=0 implies 0: there is no list on the device then.  The archives are the same either way. */
+uint32_t zpq_last_device_coded_blocks(void);
 /* Runs a tiny kernel exercising the cross-lane idioms (DPP reduction, readlane,
  * bpermute); out8[0..5] must equal {2016, 21344, 123, 2016, 133, 13671}. */
 int zpq_selftest(int32_t out8[8]);
@@ -312,6 +322,15 @@ int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, cons
                                  size_t* outlen);
 int zpq_lz77_tokens_host(const char* xmethod, uint8_t* data, uint32_t n, uint32_t* tokens4, size_t cap, size_t* count);
 int zpq_lz77_serialize(const char* xmethod, const uint8_t* data, uint32_t n, const uint32_t* tokens4, size_t ntok, uint8_t* out, size_t cap, size_t* len);
+/* zpq_lz77_serialize for a batch, with the codes written on the device (device/lz77_codes_kernel.h): token lists tokens4[b]
+ * (ntok[b] matches of 4 x uint32) over the already filtered blocks data[b] of len[b] bytes; out[b] receives block b's stream,
+ * outlen[b] its size.  The contract of the host's entry, list by list: every size is reported also when some buffer is too
+ * small (ZPQ_E_OVERFLOW; nothing is written then), a list the host's coder refuses -- matches out of order, offset 0 or
+ * beyond the position, length 0, a span past the end of the block -- is refused with ZPQ_E_DEVICE and nothing is emitted.
+ * ZPQ_E_UNSUPPORTED with a note in zpq_last_error when there is no device or the batch lies outside the device's range: blocks
+ * below 2^24 bytes, at most 65 535 blocks, 2 GiB per batch, an LZ77 method of level 1 or 2. */
+int zpq_lz77_serialize_device(const char* xmethod, const uint8_t* const* data, const uint32_t* len, const uint32_t* const* tokens4, const size_t* ntok,
+                              uint32_t nblocks, uint8_t* const* out, const size_t* cap, size_t* outlen);
 void zpq_e8e9(uint8_t* data, uint32_t n);      /* e8e9 (libzpaq.cpp:6450-6459), in place */
 /* Compiler alone (libzpaq.cpp:2698): ZPAQL source text -> header / PCOMP bytes. */
 int zpq_assemble(const char* config, const int* args9, uint8_t* hcomp, size_t hcap,

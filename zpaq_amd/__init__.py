@@ -80,6 +80,10 @@ def lib():
     L.zpq_decode_device.argtypes = L.zpq_encode_device.argtypes
     L.zpq_last_hash_parse_blocks.restype = C.c_uint32
     L.zpq_last_hash_parse_blocks.argtypes = []
+    L.zpq_last_device_coded_blocks.restype = C.c_uint32
+    L.zpq_last_device_coded_blocks.argtypes = []
+    L.zpq_lz77_serialize_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t),
+                                            C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -256,6 +260,33 @@ def compress_blocks(blocks: Sequence, method: str, filenames: Optional[Sequence[
 def last_hash_parse_blocks() -> int:
     """Blocks of the last compress_blocks call whose hash-table LZ77 parse (method 1, ...) ran on the device."""
     return int(lib().zpq_last_hash_parse_blocks())
+
+
+def last_device_coded_blocks() -> int:
+    """Blocks of the last compress_blocks call whose LZ77 stream was written on the device (ZPAQ_AMD_DEVICE_CODES)."""
+    return int(lib().zpq_last_device_coded_blocks())
+
+
+def lz77_serialize_device(xmethod: str, blocks: Sequence, tokens: Sequence, caps: Optional[Sequence[int]] = None):
+    """zpq_lz77_serialize_device: LZBuffer's codes of token lists (bytes, 16 per match: i, off, len, blit) over already
+    filtered blocks, written on the device.  Returns (return code, streams, sizes); caps = the output capacities
+    (default: room for any valid list)."""
+    n = len(blocks)
+    ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in blocks]
+    tks = [np.frombuffer(bytes(t), np.uint32).copy() if len(t) else np.zeros(4, np.uint32) for t in tokens]
+    caps = [2 * a.size + 4096 for a in ins] if caps is None else [int(c) for c in caps]
+    outs = [np.zeros(max(c, 1), np.uint8) for c in caps]
+    u32p = C.POINTER(C.c_uint32)
+    IA = (_u8p * n)(*[_p(a) for a in ins])
+    IL = (C.c_uint32 * n)(*[len(x) for x in blocks])
+    TA = (u32p * n)(*[t.ctypes.data_as(u32p) for t in tks])
+    TN = (C.c_size_t * n)(*[len(t) // 16 for t in tokens])
+    OA = (_u8p * n)(*[_p(a) for a in outs])
+    OC = (C.c_size_t * n)(*caps)
+    OL = (C.c_size_t * n)()
+    rc = lib().zpq_lz77_serialize_device(xmethod.encode(), IA, IL, TA, TN, n, OA, OC, OL)
+    sizes = [int(x) for x in OL]
+    return rc, [outs[i][:min(sizes[i], caps[i])].tobytes() for i in range(n)], sizes
 
 
 def compress_block(data, method: str, filename: Optional[str] = None, comment: Optional[str] = None,

@@ -539,13 +539,15 @@ int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, cons
   }
   std::vector<SortOut> outs;
   std::string note;
-  if (!(hashed ? engine_hash_preprocess(jobs, outs, note) : engine_sort_preprocess(jobs, outs, note))) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
+  const int codes = device_codes_mode();
+  if (!(hashed ? engine_hash_preprocess(jobs, outs, note, codes) : engine_sort_preprocess(jobs, outs, note, codes))) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
   std::vector<std::vector<U8>> pres(n);
   bool fits = true;
   for (uint32_t i = 0; i < n; ++i) {
     std::vector<U8>& pre = pres[i];
     if (len[i] == 0) (void)preprocess_block(data[i], 0, args, pre, nullptr, true);
     else if (jobs[i].kind == 3) pre.swap(outs[i].bwt);
+    else if (outs[i].coded) pre.swap(outs[i].codes);
     else lz77_serialize(data[i], len[i], args, outs[i].toks.data(), outs[i].toks.size(), pre);
     outlen[i] = pre.size();                               // (every size is reported, also when some buffer is too small)
     fits = fits && pre.size() <= cap[i];
@@ -554,6 +556,36 @@ int zpq_preprocess_blocks_device(const char* xmethod, uint8_t* const* data, cons
   for (uint32_t i = 0; i < n; ++i)
     if (!pres[i].empty()) memcpy(out[i], pres[i].data(), pres[i].size());
   guard.keep = true;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+// zpq_lz77_serialize for a batch, with the codes written on the device (device/lz77_codes_kernel.h)
+int zpq_lz77_serialize_device(const char* xmethod, const uint8_t* const* data, const uint32_t* len, const uint32_t* const* tokens4, const size_t* ntok,
+                              uint32_t nblocks, uint8_t* const* out, const size_t* cap, size_t* outlen) {
+  ZPQ_TRY
+  if (nblocks && (!data || !len || !tokens4 || !ntok || !out || !cap || !outlen)) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  lz_args(xmethod, args);
+  std::vector<CodeJob> jobs;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    if ((!data[i] && len[i]) || (!tokens4[i] && ntok[i])) fail(ZPQ_E_ARG, "null argument");
+    jobs.push_back(CodeJob{data[i], len[i], (U32)(args[1] & 3), (U32)args[2], lz_offset_rb(args), (const LzToken*)tokens4[i], ntok[i]});
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "coding on the device unavailable: no device");
+  std::vector<std::vector<U8>> pres;
+  std::string note;
+  const int got = engine_lz77_codes(jobs, pres, note);
+  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "coding on the device unavailable: " + note);
+  if (got == 0) fail(ZPQ_E_DEVICE, note);
+  bool fits = true;
+  for (uint32_t i = 0; i < nblocks; ++i) {
+    outlen[i] = pres[i].size();                           // (every size is reported, also when some buffer is too small)
+    fits = fits && pres[i].size() <= cap[i];
+  }
+  if (!fits) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  for (uint32_t i = 0; i < nblocks; ++i)
+    if (!pres[i].empty()) memcpy(out[i], pres[i].data(), pres[i].size());
   return ZPQ_OK;
   ZPQ_CATCH
 }
@@ -575,6 +607,7 @@ int zpq_last_api_timing(double out[8]) {
 }
 
 uint32_t zpq_last_hash_parse_blocks(void) { return last_api_timing().hash_parse_blocks; }
+uint32_t zpq_last_device_coded_blocks(void) { return last_api_timing().device_coded_blocks; }
 
 size_t zpq_table(int which, void* out, size_t cap) {
   try {

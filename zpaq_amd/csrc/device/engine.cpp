@@ -1669,7 +1669,69 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
   return true;
 }
 
-bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note) {
+// Stages (c) and (d) of device/lz77_codes_kernel.h, behind launch_lz77_code_lengths on e.stream: the sizes and the error word come
+// back, the streams are placed back to back (every start on a word) in the `room` bytes at d_out, emitted there and downloaded
+// into dst[b] (null: not a block of kind 1 / 2).  Sizes first, then emission: a degenerate list can expand a block, no bound is
+// guessed.  false + note: a list the host's coder refuses or an incomplete one (*refused says which), or no room.
+namespace {
+bool finish_lz77_codes(Engine& e, const std::vector<LzBlock>& blk, const uint8_t* d_in, uint64_t total, const LzBlock* d_blk, const LzTok* d_toks,
+                       const uint32_t* d_counts, const LzCodes& c, uint64_t* d_ooff, uint8_t* d_out, uint64_t room,
+                       const std::vector<std::vector<U8>*>& dst, std::string& note, uint32_t* refused) {
+  const size_t n = blk.size();
+  std::vector<uint32_t> sizes(n + 1);
+  HIP_CHECK(hipMemcpyAsync(sizes.data(), c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (refused) *refused = sizes[n];
+  if (sizes[n]) { note = (sizes[n] & kLzcErrList) ? "LZ77 token list refused by the coder's checks" : "LZ77 token list overflowed"; return false; }
+  std::vector<uint64_t> ooff(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) ooff[i + 1] = ooff[i] + (((uint64_t)sizes[i] + 3) & ~3ull);
+  if (ooff[n] > room) { note = "the coded streams do not fit the device's output buffer"; return false; }
+  if (!ooff[n]) return true;
+  HIP_CHECK(hipMemcpyAsync(d_ooff, ooff.data(), 8 * (n + 1), hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemsetAsync(d_out, 0, ooff[n], e.stream));
+  const hipError_t rc = launch_lz77_emit(d_in, d_blk, (uint32_t)n, total, d_toks, d_counts, c, d_ooff, d_out, e.stream);
+  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 coder failed: ") + hipGetErrorString(rc); return false; }
+  for (size_t i = 0; i < n; ++i) {
+    if (!dst[i]) continue;
+    dst[i]->resize(sizes[i]);
+    if (sizes[i]) HIP_CHECK(hipMemcpyAsync(dst[i]->data(), d_out + ooff[i], sizes[i], hipMemcpyDeviceToHost, e.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  return true;
+}
+// codes == 2: does writing the codes here pay for this batch?  The sizes and the counts are on the device behind the walk.
+bool codes_pay(Engine& e, const std::vector<LzBlock>& blk, const LzCodes& c, const uint32_t* d_counts, uint64_t total) {
+  const size_t n = blk.size();
+  std::vector<uint32_t> sizes(n + 1), cnt(n);
+  HIP_CHECK(hipMemcpyAsync(sizes.data(), c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipMemcpyAsync(cnt.data(), d_counts, 4 * n, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (sizes[n]) return true;                         // (the error word: finish_lz77_codes reports it)
+  uint64_t matches = 0, bytes = 0;
+  for (size_t i = 0; i < n; ++i) { matches += cnt[i]; bytes += sizes[i]; }
+  return lz_codes_pay(matches, bytes, total);
+}
+// the coder's share of a parse call's output buffer, behind `at`: sizes + error word, the streams' places, lengths / offsets, scan scratch
+struct CodesLayout { uint64_t o_sizes, o_ooff, o_pos, o_tmp, end; LzCodes c; };
+CodesLayout codes_layout(uint64_t at, size_t n, uint64_t nslots) {
+  CodesLayout L;
+  L.o_sizes = (at + 255) & ~255ull;
+  L.o_ooff = (L.o_sizes + 4 * (n + 1) + 255) & ~255ull;
+  L.o_pos = (L.o_ooff + 8 * (n + 1) + 255) & ~255ull;
+  L.o_tmp = (L.o_pos + 8 * (nslots + 1) + 255) & ~255ull;
+  L.c.nslots = nslots;
+  L.c.tmp_bytes = lzc_scan_bytes(nslots);
+  L.end = L.o_tmp + L.c.tmp_bytes;
+  return L;
+}
+void codes_bind(CodesLayout& L, uint8_t* base) {
+  L.c.pos = (uint64_t*)(base + L.o_pos);
+  L.c.tmp = base + L.o_tmp;
+  L.c.sizes = (uint32_t*)(base + L.o_sizes);
+}
+}  // namespace
+
+bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes) {
   const size_t n = jobs.size();
   out.assign(n, SortOut());
   uint64_t total = 0, ntok = 0, bwt_bytes = 0;
@@ -1684,9 +1746,10 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
     B.n = j.n;
     B.kind = j.n ? j.kind : 0u;
     B.min_match = j.min_match; B.lookahead = j.lookahead; B.bucket = j.bucket; B.checkbits = j.checkbits;
+    B.rb = j.rb;
+    B.tok_off = ntok;                                // (every block: the coder's item slots are found by it)
     if (B.kind == 1 || B.kind == 2) {
       if (j.min_match < 1 || j.lookahead > 255 || j.checkbits < 1 || j.checkbits > 31) { note = "LZ77 parameters outside the device parser's range"; return false; }
-      B.tok_off = ntok;
       B.tok_cap = j.n / j.min_match + 2;
       ntok += B.tok_cap;
       any_lz = true;
@@ -1713,7 +1776,11 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   const uint64_t o_cnt = (o_bwt + bwt_bytes + 255) & ~255ull;
   const uint64_t o_idx = o_cnt + 4 * n;
   const uint64_t o_blk = (o_idx + 4 * n + 255) & ~255ull;
-  const uint64_t out_bytes = o_blk + n * sizeof(LzBlock) + 256;
+  if (!any_lz) codes = 0;
+  // ... and the coder's arrays (device/lz77_codes_kernel.h); the streams themselves take the place of the decisions, which are
+  // dead behind the walk
+  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
+  const uint64_t out_bytes = (codes ? cl.end : o_blk + n * sizeof(LzBlock)) + 256;
   if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "sort + parse workspace exceeds the device budget"; return false; }
   e.io_in.ensure(in_bytes + 64);
   e.io_out.ensure(out_bytes);
@@ -1736,14 +1803,25 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   HIP_CHECK(hipMemcpyAsync(meta + ((n * 8 + 15) & ~15ull), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 8 * n, e.stream));
+  if (codes) { codes_bind(cl, ob); HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream)); }
   uint32_t rounds = 0;
   SaSideArrays side;
   hipError_t rc = build_suffix_arrays((const uint8_t* const*)meta, (const uint64_t*)(meta + ((n * 8 + 15) & ~15ull)), (uint32_t)n, total, max_len,
                                       (uint32_t*)ob, e.arena.p, e.arena.cap, e.stream, &rounds, &side);
   if (rc == hipSuccess)
     rc = launch_sort_preprocessors((const uint8_t*)e.io_in.p, (const uint32_t*)ob, side, (const LzBlock*)(ob + o_blk), (uint32_t)n, total, any_lz, any_bwt,
-                                   ob + o_res, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), ob + o_bwt, (uint32_t*)(ob + o_idx), e.stream);
+                                   ob + o_res, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), ob + o_bwt, (uint32_t*)(ob + o_idx), e.stream,
+                                   codes ? &cl.c : nullptr);
   if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device sort / parse failed: ") + hipGetErrorString(rc); return false; }
+  if (codes == 2 && !codes_pay(e, blk, cl.c, (const uint32_t*)(ob + o_cnt), total)) codes = 0;     // (the lists come back, as without the coder)
+  if (codes) {
+    std::vector<std::vector<U8>*> dst(n, nullptr);
+    for (size_t i = 0; i < n; ++i)
+      if (blk[i].kind == 1 || blk[i].kind == 2) { dst[i] = &out[i].codes; out[i].coded = true; }
+    if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ob + o_blk), (const LzTok*)(ob + o_tok), (const uint32_t*)(ob + o_cnt),
+                           cl.c, (uint64_t*)(ob + cl.o_ooff), ob + o_res, 16 * total, dst, note, nullptr))
+      return false;
+  }
   std::vector<uint32_t> cnt(2 * n);
   HIP_CHECK(hipMemcpyAsync(cnt.data(), ob + o_cnt, 8 * n, hipMemcpyDeviceToHost, e.stream));
   HIP_CHECK(hipStreamSynchronize(e.stream));
@@ -1751,6 +1829,7 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   for (size_t i = 0; i < n; ++i) {
     const LzBlock& B = blk[i];
     if (B.kind == 1 || B.kind == 2) {
+      if (codes) continue;                                          // (its stream is there already)
       if (cnt[i] > B.tok_cap) { note = "LZ77 token list overflowed"; return false; }
       out[i].toks.resize(cnt[i]);
       if (cnt[i]) HIP_CHECK(hipMemcpyAsync(out[i].toks.data(), ob + o_tok + 16 * B.tok_off, 16ull * cnt[i], hipMemcpyDeviceToHost, e.stream));
@@ -1766,7 +1845,7 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   return true;
 }
 
-bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note) {
+bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes) {
   const size_t n = jobs.size();
   out.assign(n, SortOut());
   uint64_t total = 0, ntok = 0, nkeys = 0, nidx = 0;
@@ -1781,6 +1860,7 @@ bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
     B.kind = j.n ? j.kind : 0u;
     B.min_match = j.min_match; B.lookahead = j.lookahead; B.bucket = j.bucket; B.checkbits = j.checkbits;
     B.min_match2 = j.min_match2; B.ht_bits = j.ht_bits;
+    B.rb = j.rb;
     B.tok_off = ntok;
     B.tok_cap = j.n / j.min_match + 2;
     ntok += B.tok_cap;
@@ -1800,7 +1880,9 @@ bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   const uint64_t o_tok = 16 * total;
   const uint64_t o_cnt = (o_tok + 16 * ntok + 255) & ~255ull;
   const uint64_t o_blk = (o_cnt + 4 * n + 255) & ~255ull;
-  const uint64_t out_bytes = o_blk + n * sizeof(LzBlock) + 256;
+  // ... and the coder's arrays; the streams take the place of the decisions (device/lz77_codes_kernel.h)
+  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
+  const uint64_t out_bytes = (codes ? cl.end : o_blk + n * sizeof(LzBlock)) + 256;
   if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "hash parse workspace exceeds the device budget"; return false; }
   e.io_in.ensure(in_bytes + 64);
   e.io_out.ensure(out_bytes);
@@ -1814,9 +1896,21 @@ bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage, total, hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 4 * n, e.stream));
+  if (codes) { codes_bind(cl, ob); HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream)); }
   const hipError_t rc = launch_hash_parse((const uint8_t*)e.io_in.p, (const LzBlock*)(ob + o_blk), (uint32_t)n, total, nkeys, nidx, e.arena.p, e.arena.cap,
-                                          ob, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), e.stream);
+                                          ob, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), e.stream, codes ? &cl.c : nullptr);
   if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device hash parse failed: ") + hipGetErrorString(rc); return false; }
+  if (codes == 2 && !codes_pay(e, blk, cl.c, (const uint32_t*)(ob + o_cnt), total)) codes = 0;     // (the lists come back, as without the coder)
+  if (codes) {
+    std::vector<std::vector<U8>*> dst(n, nullptr);
+    for (size_t i = 0; i < n; ++i)
+      if (blk[i].kind == 1 || blk[i].kind == 2) { dst[i] = &out[i].codes; out[i].coded = true; }
+    if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ob + o_blk), (const LzTok*)(ob + o_tok), (const uint32_t*)(ob + o_cnt),
+                           cl.c, (uint64_t*)(ob + cl.o_ooff), ob, 16 * total, dst, note, nullptr))
+      return false;
+    note = "device, " + std::to_string(nkeys) + " keys, coded there";
+    return true;
+  }
   std::vector<uint32_t> cnt(n);
   HIP_CHECK(hipMemcpyAsync(cnt.data(), ob + o_cnt, 4 * n, hipMemcpyDeviceToHost, e.stream));
   HIP_CHECK(hipStreamSynchronize(e.stream));
@@ -1829,6 +1923,79 @@ bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   HIP_CHECK(hipStreamSynchronize(e.stream));
   note = "device, " + std::to_string(nkeys) + " keys";
   return true;
+}
+
+int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<U8>>& out, std::string& note) {
+  const size_t n = jobs.size();
+  out.assign(n, std::vector<U8>());
+  if (!n) return 1;
+  uint64_t total = 0, ntok = 0;
+  std::vector<LzBlock> blk(n);
+  std::vector<uint32_t> cnt(n);
+  bool in_range = n <= 65535;
+  for (size_t i = 0; i < n && in_range; ++i) {
+    const CodeJob& j = jobs[i];
+    in_range = j.n < (1u << 24) && (j.kind == 1 || j.kind == 2) && j.min_match >= 1 && j.min_match <= 255 && j.rb <= 7 && j.ntok <= (size_t)j.n + 1;
+    LzBlock& B = blk[i];
+    memset(&B, 0, sizeof(B));
+    B.off = total;
+    B.n = j.n;
+    B.kind = j.kind;                                 // (also for an empty block: a list over it must be refused)
+    B.min_match = j.min_match;
+    B.rb = j.rb;
+    B.tok_off = ntok;
+    B.tok_cap = cnt[i] = (uint32_t)j.ntok;
+    ntok += j.ntok;
+    total += j.n;
+  }
+  // (a list of more than n + 1 tokens cannot be in order: positions rise strictly -- but saying so is the kernel's job; such a
+  // list is merely outside what the buffers are sized for)
+  if (!in_range || total >= (1ull << 31)) { note = "batch outside the device coder's range"; return -1; }
+  Engine& e = eng();
+  std::lock_guard<std::mutex> g(e.mu);
+  require_ready(e);
+  bind_device(e);
+  wait_in_flight(e);
+  // the arena buffer (idle between batches): tokens, counts, the block table, the coder's arrays; inputs in io_in, streams in io_out
+  const uint64_t o_cnt = (16 * ntok + 255) & ~255ull;
+  const uint64_t o_blk = (o_cnt + 4 * n + 255) & ~255ull;
+  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
+  const uint64_t ws = cl.end + 256, in_bytes = (total + 255) & ~255ull;
+  if (ws + in_bytes + (1u << 20) > e.budget) { note = "coder workspace exceeds the device budget"; return -1; }
+  e.io_in.ensure(in_bytes + 64);
+  e.arena.ensure(ws);
+  uint8_t* const ab = (uint8_t*)e.arena.p;
+  codes_bind(cl, ab);
+  std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
+  std::vector<LzToken> toks(ntok + 1);
+  for (size_t i = 0; i < n; ++i) {
+    if (jobs[i].n) memcpy(stage.get() + blk[i].off, jobs[i].data, jobs[i].n);
+    if (jobs[i].ntok) memcpy(toks.data() + blk[i].tok_off, jobs[i].toks, 16 * jobs[i].ntok);
+  }
+  static_assert(sizeof(LzTok) == sizeof(LzToken) && sizeof(LzTok) == 16, "token layouts");
+  if (total) HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), total, hipMemcpyHostToDevice, e.stream));
+  if (ntok) HIP_CHECK(hipMemcpyAsync(ab, toks.data(), 16 * ntok, hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemcpyAsync(ab + o_cnt, cnt.data(), 4 * n, hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemcpyAsync(ab + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream));
+  const hipError_t rc = launch_lz77_code_lengths((const LzBlock*)(ab + o_blk), (uint32_t)n, (const LzTok*)ab, (const uint32_t*)(ab + o_cnt), cl.c, e.stream);
+  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 coder failed: ") + hipGetErrorString(rc); return -1; }
+  // sizes first: the streams' room is claimed once they are known
+  std::vector<uint32_t> sizes(n + 1);
+  HIP_CHECK(hipMemcpyAsync(sizes.data(), cl.c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (sizes[n]) { note = "LZ77 token list refused by the coder's checks"; return 0; }
+  uint64_t room = 0;
+  for (size_t i = 0; i < n; ++i) room += ((uint64_t)sizes[i] + 3) & ~3ull;
+  if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "the coded streams exceed the device budget"; return -1; }
+  e.io_out.ensure(room + 64);
+  std::vector<std::vector<U8>*> dst(n);
+  for (size_t i = 0; i < n; ++i) dst[i] = &out[i];
+  uint32_t refused = 0;
+  if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ab + o_blk), (const LzTok*)ab, (const uint32_t*)(ab + o_cnt), cl.c,
+                         (uint64_t*)(ab + cl.o_ooff), (uint8_t*)e.io_out.p, room, dst, note, &refused))
+    return refused ? 0 : -1;
+  return 1;
 }
 
 int engine_jit_threads() { return jit_threads(); }

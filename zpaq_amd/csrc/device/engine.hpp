@@ -73,24 +73,36 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
 // The pre-processors behind the sort for a whole batch on the device (device/lz77_kernel.h): blocks of kind 1 / 2 come back as
 // the LZ77 parse's list of matches (host/preproc.cpp lz77_serialize codes it), blocks of kind 3 as the BWT stream
 // preprocess_block would make (n + 5 bytes).  false + note when the device declines (then the host does it all).
-struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0; };   // (the last two: hash_job)
-struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; };
-bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note);
+// codes: LZBuffer's codes are written on the device as well (device/lz77_codes_kernel.h) -- a block of kind 1 / 2 then comes back
+// as its finished stream in SortOut::codes (coded = true) and its list of matches is not downloaded.
+struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0, rb = 0; };   // (min_match2, ht_bits: hash_job; rb: the coder)
+struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; };
+// codes: 0 the lists come back; 1 the streams; 2 the streams when that pays -- decided per batch once the sizes are known, by
+// lz_codes_pay below (DESIGN 4.5.2 has the measurement behind it)
+bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes = 0);
+// The device writes the codes of a batch whose streams are smaller than its lists (16 bytes per match: less comes back over PCIe
+// and no host core walks the blocks) unless they are below 1 % of the input (long repeats: either way moves next to nothing, and
+// no gain was measured).  An incompressible batch has no matches: its list is empty, its stream is the input.
+inline bool lz_codes_pay(U64 matches, U64 stream_bytes, U64 input_bytes) { return 16 * matches > stream_bytes && 100 * stream_bytes >= input_bytes; }
+inline U32 lz_offset_rb(const int args[9]) { return args[0] > 4 ? (U32)(args[0] - 4) : 0u; }     // low offset bits level 1 writes as they are
 // the job of a block whose method has these args (LZBuffer's parameters: libzpaq.cpp:6647-6692)
 inline SortJob sort_job(const U8* data, U32 n, const int args[9]) {
   const U32 level = (U32)(args[1] & 3);
   if (level == 3) return SortJob{data, n, 3u, 0u, 0u, 0u, 0u};
-  return SortJob{data, n, level, (U32)args[2], (U32)args[6], args[4] >= 0 && args[4] < 31 ? (1u << args[4]) - 1u : 0x7FFFFFFFu, (U32)(17 + args[0])};
+  SortJob j{data, n, level, (U32)args[2], (U32)args[6], args[4] >= 0 && args[4] < 31 ? (1u << args[4]) - 1u : 0x7FFFFFFFu, (U32)(17 + args[0])};
+  j.rb = lz_offset_rb(args);
+  return j;
 }
 // The LZ77 parse through LZBuffer's hash table (args[5] - args[0] < 21: method 1, method 2 below type 64, ...) for a whole batch on
 // the device (device/lz77_hash_kernel.h): every block comes back as its list of matches, like the kind 1 / 2 blocks of
 // engine_sort_preprocess.  Same buffers, same contract: false + note when the device declines or fails (then the host parses),
 // nothing of the caller's is touched.
-bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note);
+bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes = 0);
 inline SortJob hash_job(const U8* data, U32 n, const int args[9]) {
   SortJob j{data, n, (U32)(args[1] & 3), (U32)args[2], (U32)args[6], args[4] >= 0 && args[4] < 31 ? (1u << args[4]) - 1u : 0x7FFFFFFFu, (U32)(12 - args[0])};
   j.min_match2 = (U32)args[3];
   j.ht_bits = (U32)args[5];
+  j.rb = lz_offset_rb(args);
   return j;
 }
 // What the device's hash-table parser takes (everything else stays on the host): blocks below 2^24 bytes, tables of up to 2^24
@@ -101,6 +113,11 @@ inline bool hash_job_in_range(const SortJob& j) {
   return (j.kind == 1 || j.kind == 2) && j.n < (1u << 24) && j.ht_bits >= 1 && j.ht_bits <= 24 && j.bucket < (1u << j.ht_bits) && j.lookahead <= 255 &&
          j.min_match >= 2 && j.min_match <= 255 && j.min_match2 <= 255 && (j.kind == 1 || j.min_match <= 64) && j.checkbits >= 1 && j.checkbits <= 12;
 }
+// LZBuffer's codes for given token lists over given (already filtered) blocks, on the device: what host/preproc.cpp
+// lz77_serialize writes, list by list.  1: out[i] holds stream i; 0: some list is one emit_tokens refuses (nothing is emitted);
+// -1 + note: the device declines (blocks of 2^24 bytes and more, more than 65 535 blocks, 2 GiB per batch, memory).
+struct CodeJob { const U8* data; U32 n, kind, min_match, rb; const LzToken* toks; size_t ntok; };
+int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<U8>>& out, std::string& note);
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)
 

@@ -197,11 +197,13 @@ struct LzBlock {            // one per block of the batch
   uint32_t idx_bits;        // its index has 2^idx_bits + 1 entries: where the keys of each slot prefix start
   uint32_t nkeys;           // keys of the block: ins_end x (1 or 2)
   uint32_t ins_end;         // positions below max(0, n - minMatchBoth) are inserted, the hashes stand still from there on
-  uint32_t pad;
+  uint32_t rb;              // max(args[0] - 4, 0): low offset bits the bit-packed code writes as they are (device/lz77_codes_kernel.h)
   uint64_t key_off;         // its first key in the batch's key array
   uint64_t idx_off;         // its first entry in the batch's index array
 };
 struct LzTok { uint32_t i, off, len, blit; };            // = host/common.hpp LzToken
+// the error word of the device's coder (device/lz77_codes_kernel.h): a list emit_tokens refuses; more tokens than slots
+static const uint32_t kLzcErrList = 1u, kLzcErrCount = 2u;
 // The derived fields of a hash-table block (n, min_match, min_match2, lookahead, bucket, ht_bits set; bucket < 2^ht_bits): what
 // is inserted, and an index that resolves slot prefixes down to about 8 keys each -- never finer than a bucket, because the slots
 // one search reads (h ^ k, k <= bucket) must share their prefix.  nkeys / nidx: running sums over the batch.

@@ -13,6 +13,8 @@ namespace zpq {
 struct SaSideArrays { uint32_t* rank = nullptr; uint16_t* blk = nullptr; };
 // device memory build_suffix_arrays needs for `total` bytes of input in `nblocks` blocks
 size_t sa_workspace_bytes(uint64_t total, uint32_t nblocks);
+// what the stages behind the walk that write LZBuffer's codes need (described with launch_lz77_code_lengths below)
+struct LzCodes { uint64_t nslots = 0; uint64_t* pos = nullptr; void* tmp = nullptr; size_t tmp_bytes = 0; uint32_t* sizes = nullptr; };
 // d_in[b] -> block b's bytes on the device; d_off[0..nblocks] = exclusive prefix sums of the lengths; d_sa: the arrays back
 // to back (block b's at d_sa + off[b]); max_len < 2^24, nblocks < 65536, total < 2^32.  Synchronises `st` once per round.
 hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off, uint32_t nblocks, uint64_t total, uint32_t max_len,
@@ -23,12 +25,25 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
 // bytes back to back like the arrays.
 hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_all, const SaSideArrays& side, const LzBlock* blocks, uint32_t nblocks,
                                      uint64_t total, bool any_lz, bool any_bwt, void* res, LzTok* toks, uint32_t* counts, uint8_t* bwt_out,
-                                     uint32_t* bwt_idx, hipStream_t st);
+                                     uint32_t* bwt_idx, hipStream_t st, const LzCodes* codes = nullptr);
 // The LZ77 parse through LZBuffer's hash table for a batch (device/lz77_hash_kernel.h): keys, one radix sort, the index of slot
 // prefixes, the search (16 bytes of decisions per element in `res`), then lz77_walk_kernel as behind the sort.  The caller fills
 // blocks[b].ht_bits / min_match2 / ins_end / nkeys / key_off / idx_bits / idx_off; nkeys, nidx: the sums of the blocks' keys and
 // index entries (2^idx_bits + 1 each).  ws: lzh_workspace_bytes(total, nkeys, nidx) bytes of device memory.
 size_t lzh_workspace_bytes(uint64_t total, uint64_t nkeys, uint64_t nidx);
 hipError_t launch_hash_parse(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, uint64_t nkeys, uint64_t nidx, void* ws,
-                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st);
+                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st, const LzCodes* codes = nullptr);
+// LZBuffer's codes from the lists the walk leaves (device/lz77_codes_kernel.h).  Block b owns the item slots tok_off + b ..
+// tok_off + b + tok_cap (one per token slot and one for the end of the block); nslots = their number over the batch.
+//   pos     nslots + 1 words of 64 bits: every item's length in bits, then (in place) its offset in the batch
+//   tmp     lzc_scan_bytes(nslots) bytes for the scan
+//   sizes   nblocks + 1 words: every block's stream length in bytes, then the error word (zeroed by the caller; not 0: a list
+//           emit_tokens refuses, or more tokens than slots -- then nothing may be emitted)
+// launch_lz77_code_lengths runs behind the walk (both launchers above take `codes` and do that); the caller reads `sizes`, places
+// the streams -- out_off[b] = block b's first byte in `out`, a multiple of 4, out_off[nblocks] = the end of the last one's room;
+// nblocks + 1 words on the device -- zeroes `out` and calls launch_lz77_emit.
+size_t lzc_scan_bytes(uint64_t nslots);
+hipError_t launch_lz77_code_lengths(const LzBlock* blocks, uint32_t nblocks, const LzTok* toks, const uint32_t* counts, const LzCodes& c, hipStream_t st);
+hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, const LzTok* toks, const uint32_t* counts,
+                            const LzCodes& c, const uint64_t* out_off, uint8_t* out, hipStream_t st);
 }  // namespace zpq

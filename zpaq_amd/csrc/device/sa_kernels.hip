@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "lz77_codes_kernel.h"
 #include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
 #include "sa_kernels.h"
@@ -102,6 +103,22 @@ __global__ __launch_bounds__(256) void lzh_search_kernel(const uint8_t* in_all, 
   lzh_search_body(in_all, keys, idx, blk, blocks, total, res);
 }
 
+__global__ __launch_bounds__(256) void lzc_len_kernel(const LzBlock* blocks, uint32_t nblocks, uint64_t nslots, const LzTok* toks, const uint32_t* counts,
+                                                      uint64_t* len, uint32_t* err) {
+  lzc_len_body(blocks, nblocks, nslots, toks, counts, len, err);
+}
+__global__ __launch_bounds__(256) void lzc_sizes_kernel(const LzBlock* blocks, uint32_t nblocks, uint64_t nslots, const uint64_t* pos, uint32_t* sizes) {
+  lzc_sizes_body(blocks, nblocks, nslots, pos, sizes);
+}
+__global__ __launch_bounds__(256) void lzc_match_kernel(const LzBlock* blocks, uint32_t nblocks, uint64_t nslots, const LzTok* toks, const uint32_t* counts,
+                                                        const uint64_t* pos, const uint64_t* out_off, uint8_t* out) {
+  lzc_match_body(blocks, nblocks, nslots, toks, counts, pos, out_off, out);
+}
+__global__ __launch_bounds__(256) void lzc_literal_kernel(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, const LzTok* toks,
+                                                          const uint32_t* counts, const uint64_t* pos, const uint64_t* out_off, uint8_t* out) {
+  lzc_literal_body(in_all, blocks, nblocks, total, toks, counts, pos, out_off, out);
+}
+
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -166,12 +183,16 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
 
 hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_all, const SaSideArrays& side, const LzBlock* blocks, uint32_t nblocks,
                                      uint64_t total, bool any_lz, bool any_bwt, void* res, LzTok* toks, uint32_t* counts, uint8_t* bwt_out,
-                                     uint32_t* bwt_idx, hipStream_t st) {
+                                     uint32_t* bwt_idx, hipStream_t st, const LzCodes* codes) {
   if (!total || !nblocks) return hipSuccess;
   const unsigned g = grid_for(total);
   if (any_lz) {
     hipLaunchKernelGGL(lz77_search_kernel, dim3(g), dim3(256), 0, st, in_all, sa_all, (const uint32_t*)side.rank, (const uint16_t*)side.blk, blocks, total, (uint4*)res);
     hipLaunchKernelGGL(lz77_walk_kernel, dim3(nblocks), dim3(64), 0, st, blocks, (const uint4*)res, toks, counts);
+    if (codes) {
+      const hipError_t e = launch_lz77_code_lengths(blocks, nblocks, toks, counts, *codes, st);
+      if (e != hipSuccess) return e;
+    }
   }
   if (any_bwt)
     hipLaunchKernelGGL(bwt_emit_kernel, dim3(g), dim3(256), 0, st, in_all, sa_all, (const uint16_t*)side.blk, blocks, total, bwt_out, bwt_idx);
@@ -188,7 +209,7 @@ size_t lzh_workspace_bytes(uint64_t total, uint64_t nkeys, uint64_t nidx) {
 // The LZ77 parse through the hash table for a whole batch (device/lz77_hash_kernel.h): blocks[b] with ht_bits != 0, key_off /
 // idx_off / nkeys / ins_end / idx_bits filled in by the caller (nkeys, nidx: the sums over the batch).
 hipError_t launch_hash_parse(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, uint64_t nkeys, uint64_t nidx, void* ws,
-                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st) {
+                             size_t ws_bytes, void* res, LzTok* toks, uint32_t* counts, hipStream_t st, const LzCodes* codes) {
   if (!total || !nblocks) return hipSuccess;
   if (nblocks > 65535u || total >= (1ull << 32) || ws_bytes < lzh_workspace_bytes(total, nkeys, nidx)) return hipErrorInvalidValue;
   uint8_t* p = (uint8_t*)ws;
@@ -210,6 +231,39 @@ hipError_t launch_hash_parse(const uint8_t* in_all, const LzBlock* blocks, uint3
   hipLaunchKernelGGL(lzh_search_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, (const uint64_t*)keys2, (const uint32_t*)idx,
                      (const uint16_t*)blk, blocks, total, (uint4*)res);
   hipLaunchKernelGGL(lz77_walk_kernel, dim3(nblocks), dim3(64), 0, st, blocks, (const uint4*)res, toks, counts);
+  if (codes) {
+    const hipError_t e = launch_lz77_code_lengths(blocks, nblocks, toks, counts, *codes, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
+size_t lzc_scan_bytes(uint64_t nslots) {
+  size_t scan_tmp = 0;
+  (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(nslots + 1), rocprim::plus<uint64_t>());
+  return up256(scan_tmp) + 256;
+}
+
+// Stages (a) and (b) of device/lz77_codes_kernel.h: lengths, the scan (64-bit: 2 GiB of input is more than 2^32 bits), sizes.
+hipError_t launch_lz77_code_lengths(const LzBlock* blocks, uint32_t nblocks, const LzTok* toks, const uint32_t* counts, const LzCodes& c, hipStream_t st) {
+  if (!nblocks) return hipSuccess;
+  if (!c.pos || !c.sizes || !c.tmp || c.nslots < nblocks || c.nslots >= (1ull << 32) || c.tmp_bytes < lzc_scan_bytes(c.nslots)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lzc_len_kernel, dim3(grid_for(c.nslots + 1)), dim3(256), 0, st, blocks, nblocks, c.nslots, toks, counts, c.pos, c.sizes + nblocks);
+  size_t need = c.tmp_bytes;
+  const hipError_t e = rocprim::exclusive_scan(c.tmp, need, c.pos, c.pos, (uint64_t)0, (size_t)(c.nslots + 1), rocprim::plus<uint64_t>(), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lzc_sizes_kernel, dim3(grid_for(nblocks)), dim3(256), 0, st, blocks, nblocks, c.nslots, (const uint64_t*)c.pos, c.sizes);
+  return hipGetLastError();
+}
+
+// Stage (d): `out` is zeroed (level 1 only ever ORs into it), the streams lie where out_off says.
+hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, const LzTok* toks, const uint32_t* counts,
+                            const LzCodes& c, const uint64_t* out_off, uint8_t* out, hipStream_t st) {
+  if (!nblocks) return hipSuccess;
+  hipLaunchKernelGGL(lzc_match_kernel, dim3(grid_for(c.nslots)), dim3(256), 0, st, blocks, nblocks, c.nslots, toks, counts, (const uint64_t*)c.pos, out_off, out);
+  if (total)
+    hipLaunchKernelGGL(lzc_literal_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, blocks, nblocks, total, toks, counts, (const uint64_t*)c.pos,
+                       out_off, out);
   return hipGetLastError();
 }
 

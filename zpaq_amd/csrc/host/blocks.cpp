@@ -197,6 +197,11 @@ void parallel_blocks(size_t n, F&& fn) {
 static const size_t kHashParseMinBlocks = 4;
 static const U64 kHashParseMinBytes = 1u << 20;
 
+int device_codes_mode() {
+  const char* knob = getenv("ZPAQ_AMD_DEVICE_CODES");
+  return !knob || !knob[0] ? 2 : (knob[0] != '0' ? 1 : 0);
+}
+
 void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool dosha1,
                      std::vector<std::vector<U8>>& archives) {
   const size_t nb = in.size();
@@ -249,6 +254,10 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
   // ... and behind the sort, on the device as well (device/lz77_kernel.h): the LZ77 parse comes back as a list of matches the
   // host only has to write LZBuffer's codes for, the BWT as its bytes -- 16 bytes per match or n + 5 bytes over PCIe instead
   // of the 4 n of the array.  ZPAQ_AMD_DEVICE_PARSE=0: only the sort there, the host parses (the previous behaviour).
+  // With ZPAQ_AMD_DEVICE_CODES (default: where it pays, engine.hpp lz_codes_pay) the codes are written there too (device/lz77_codes_kernel.h): the finished stream
+  // comes back instead of the list, and no host core walks the block again.
+  const int dev_codes = device_codes_mode();
+  U32 coded_blocks = 0;
   std::vector<std::vector<U32>> dev_sa(nb);
   std::vector<SortOut> dev_pre(nb);
   std::vector<char> have_pre(nb, 0);
@@ -272,9 +281,9 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
         std::vector<SortJob> sj;
         for (size_t b : sorting) sj.push_back(sort_job(in[b].data, in[b].n, front[b].args));
         std::vector<SortOut> so;
-        try { got = engine_sort_preprocess(sj, so, note); } catch (const Failure&) { got = false; }   // (any device trouble: the next path)
+        try { got = engine_sort_preprocess(sj, so, note, dev_codes); } catch (const Failure&) { got = false; }   // (any device trouble: the next path)
         if (got)
-          for (size_t k = 0; k < sorting.size(); ++k) { dev_pre[sorting[k]] = std::move(so[k]); have_pre[sorting[k]] = 1; }
+          for (size_t k = 0; k < sorting.size(); ++k) { coded_blocks += so[k].coded; dev_pre[sorting[k]] = std::move(so[k]); have_pre[sorting[k]] = 1; }
       }
       if (!got) {
         std::vector<std::pair<const U8*, U32>> blk;
@@ -313,13 +322,14 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
       std::vector<SortOut> ho;
       std::string note;
       bool got = false;
-      try { got = engine_hash_preprocess(hj, ho, note); } catch (const Failure&) { got = false; }      // (any device trouble: the host parses)
+      try { got = engine_hash_preprocess(hj, ho, note, dev_codes); } catch (const Failure&) { got = false; }      // (any device trouble: the host parses)
       if (got)
-        for (size_t k = 0; k < hashing.size(); ++k) { dev_pre[hashing[k]] = std::move(ho[k]); have_pre[hashing[k]] = 1; }
+        for (size_t k = 0; k < hashing.size(); ++k) { coded_blocks += ho[k].coded; dev_pre[hashing[k]] = std::move(ho[k]); have_pre[hashing[k]] = 1; }
       for (size_t b : hashing) front[b].sorts = true;                 // (E8E9 is done either way)
       tm.hash_parse_blocks = got ? (U32)hashing.size() : 0;
     }
   }
+  tm.device_coded_blocks = coded_blocks;
   parallel_blocks(nb, [&](size_t b) {
     Work& w = work[b];
     const Front& f = front[b];
@@ -329,6 +339,7 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     // LZ77 / BWT / E8E9 (libzpaq.cpp:7709-7716); E8E9 rewrites the caller's buffer in place, as the reference does
     if (have_pre[b] && n > 0) {                        // parsed / transformed on the device: the coder, or nothing left to do
       if ((args[1] & 3) == 3) w.pre.swap(dev_pre[b].bwt);
+      else if (dev_pre[b].coded) w.pre.swap(dev_pre[b].codes);
       else lz77_serialize(in[b].data, n, args, dev_pre[b].toks.data(), dev_pre[b].toks.size(), w.pre);
       w.use_pre = true;
       SortOut().toks.swap(dev_pre[b].toks);

@@ -26,9 +26,13 @@ struct ApiTiming {
   double kernel_init_ms = 0, kernel_code_ms = 0;   // inside device_ms: the kernels alone (hipEvents)
   size_t blocks = 0;
   U32 hash_parse_blocks = 0;  // blocks whose hash-table LZ77 parse ran on the device (device/lz77_hash_kernel.h)
+  U32 device_coded_blocks = 0;  // blocks whose LZ77 stream was written on the device (device/lz77_codes_kernel.h)
   U32 sa_device_blocks = 0;   // blocks whose suffix array was built on the device (LZ77 / BWT pre-processors)
 };
 ApiTiming last_api_timing();
+// ZPAQ_AMD_DEVICE_CODES: LZBuffer's codes of a batch the device parsed are written there as well -- 0 never, 1 always, unset
+// (2) when it pays for the batch (device/engine.hpp lz_codes_pay)
+int device_codes_mode();
 
 // Batched libzpaq::compressBlock (libzpaq.cpp:7543-7731): one archive (tag ..
 // 255) per input, all modelled payloads coded on the device in one batch.
