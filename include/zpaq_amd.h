@@ -331,6 +331,28 @@ int zpq_lz77_serialize(const char* xmethod, const uint8_t* data, uint32_t n, con
  * below 2^24 bytes, at most 65 535 blocks, 2 GiB per batch, an LZ77 method of level 1 or 2. */
 int zpq_lz77_serialize_device(const char* xmethod, const uint8_t* const* data, const uint32_t* len, const uint32_t* const* tokens4, const size_t* ntok,
                               uint32_t nblocks, uint8_t* const* out, const size_t* cap, size_t* outlen);
+/* The method's own PCOMP program over one stream on the HOST (host/postproc.cpp): the inverse of zpq_preprocess_block, what
+ * zpq_decompress does with a segment behind the model.  A method without a program passes the stream through.  outlen always
+ * receives the size; ZPQ_E_OVERFLOW when cap is too small (nothing is written), ZPQ_E_VM when the program stops with an error. */
+int zpq_postprocess_block(const char* xmethod, const uint8_t* stream, uint32_t len, uint8_t* out, size_t cap, size_t* outlen);
+/* The same for a batch of LZ77 streams (level 1 / 2, no E8E9) on the device (device/lz77_decode_kernel.h, a wavefront per
+ * stream).  status[b]: 0 decoded -- out[b] holds, byte for byte, what zpq_postprocess_block makes of stream b, outlen[b] its
+ * size; 1 declined -- out[b] is untouched and the caller runs the program on the host: a match that reaches in front of the
+ * output, a length of 0, an output beyond the program's 2^(args[0] + 20) bytes, a field beyond the program's registers.  The
+ * device never gives a verdict on a damaged stream, and it declines no stream this library's coder writes.  How a stream ends
+ * is the program's: an unfinished code is dropped, an unfinished run of literals keeps the bytes that arrived.
+ * Every size is reported also when a buffer is too small (ZPQ_E_OVERFLOW, nothing written); ZPQ_E_UNSUPPORTED with a note in
+ * zpq_last_error without a device, for another kind of method, or outside the range (65 535 streams and 2 GiB of output per
+ * batch, 16 bytes of workspace per stream byte within the device budget). */
+int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                           uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that device/lz77_decode_kernel.h decoded.  A segment qualifies when its
+ * block has one segment and carries, byte for byte, one of the LZ77 programs without E8E9 that compressBlock's methods generate
+ * (methods 1 and 2, the LZ77 branches of 3 and 4, x.,1.. / x.,2..); E8E9 variants, BWT, custom programs and blocks of several
+ * segments never do.  ZPAQ_AMD_DEVICE_UNLZ=0|1 forces the route off or on for qualifying segments; unset it is taken by
+ * groups of 256 segments and more, the smallest batch at which it was faster than both other routes.  Any set
+ * value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  The bytes are the same either way. */
+uint32_t zpq_last_device_unlz_segments(void);
 void zpq_e8e9(uint8_t* data, uint32_t n);      /* e8e9 (libzpaq.cpp:6450-6459), in place */
 /* Compiler alone (libzpaq.cpp:2698): ZPAQL source text -> header / PCOMP bytes. */
 int zpq_assemble(const char* config, const int* args9, uint8_t* hcomp, size_t hcap,

@@ -84,6 +84,11 @@ def lib():
     L.zpq_last_device_coded_blocks.argtypes = []
     L.zpq_lz77_serialize_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t),
                                             C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.zpq_postprocess_block.argtypes = [C.c_char_p, _u8p, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.zpq_lz77_decode_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    L.zpq_last_device_unlz_segments.restype = C.c_uint32
+    L.zpq_last_device_unlz_segments.argtypes = []
     _lib = L
     return L
 
@@ -287,6 +292,47 @@ def lz77_serialize_device(xmethod: str, blocks: Sequence, tokens: Sequence, caps
     rc = lib().zpq_lz77_serialize_device(xmethod.encode(), IA, IL, TA, TN, n, OA, OC, OL)
     sizes = [int(x) for x in OL]
     return rc, [outs[i][:min(sizes[i], caps[i])].tobytes() for i in range(n)], sizes
+
+
+def postprocess_block(xmethod: str, stream, cap: Optional[int] = None):
+    """zpq_postprocess_block: the method's own PCOMP program over one stream on the host, the inverse of zpq_preprocess_block.
+    Returns (return code, output, size)."""
+    a = _arr(stream)
+    src = a if a.size else np.zeros(1, np.uint8)
+    ol = C.c_size_t(0)
+    if cap is None:                                   # ask for the size first
+        probe = np.zeros(1, np.uint8)
+        rc = lib().zpq_postprocess_block(xmethod.encode(), _p(src), a.size, _p(probe), 0, C.byref(ol))
+        if rc not in (0, 3):
+            return rc, b"", 0
+        cap = int(ol.value)
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    rc = lib().zpq_postprocess_block(xmethod.encode(), _p(src), a.size, _p(out), int(cap), C.byref(ol))
+    size = int(ol.value)
+    return rc, (out[:size].tobytes() if rc == 0 else b""), size
+
+
+def lz77_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
+    """zpq_lz77_decode_device: a batch of LZ77 streams (level 1 / 2, no E8E9) back into their blocks on the device.
+    caps = the output capacities; `guard` bytes of `fill` lie behind each.  Returns (return code, buffers -- cap + guard bytes each,
+    as the call left them --, sizes, statuses: 0 decoded, 1 declined)."""
+    n = len(streams)
+    ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in streams]
+    caps = [int(c) for c in caps]
+    outs = [np.full(max(c + guard, 1), fill, np.uint8) for c in caps]
+    IA = (_u8p * n)(*[_p(a) for a in ins])
+    IL = (C.c_uint32 * n)(*[len(x) for x in streams])
+    OA = (_u8p * n)(*[_p(a) for a in outs])
+    OC = (C.c_size_t * n)(*caps)
+    OL = (C.c_size_t * n)()
+    ST = (C.c_int32 * n)()
+    rc = lib().zpq_lz77_decode_device(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
+    return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
+
+
+def last_device_unlz_segments() -> int:
+    """Segments of the last decompress call that the device's LZ77 decoder decoded (ZPAQ_AMD_DEVICE_UNLZ)."""
+    return int(lib().zpq_last_device_unlz_segments())
 
 
 def compress_block(data, method: str, filename: Optional[str] = None, comment: Optional[str] = None,

@@ -590,6 +590,57 @@ int zpq_lz77_serialize_device(const char* xmethod, const uint8_t* const* data, c
   ZPQ_CATCH
 }
 
+// The method's own PCOMP program over one stream (host/postproc.cpp): a segment's decoded bytes are the PP header -- 0, or
+// 1 len16 program -- and the stream.
+int zpq_postprocess_block(const char* xmethod, const uint8_t* stream, uint32_t len, uint8_t* out, size_t cap, size_t* outlen) {
+  ZPQ_TRY
+  if (!xmethod || (!stream && len) || !outlen) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  const std::string cfg = make_config(xmethod, args);
+  const Assembled as = assemble(cfg.c_str(), args);
+  std::vector<U8> decoded, data;
+  decoded.reserve(1 + as.pcomp.size() + len);
+  decoded.push_back(as.pcomp.empty() ? 0 : 1);
+  decoded.insert(decoded.end(), as.pcomp.begin(), as.pcomp.end());
+  if (len) decoded.insert(decoded.end(), stream, stream + len);
+  post_process(as.hcomp, decoded, data);
+  *outlen = data.size();
+  if (data.size() > cap) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  if (!data.empty()) memcpy(out, data.data(), data.size());
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+// ... for a batch of LZ77 streams on the device (device/lz77_decode_kernel.h)
+int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                           size_t* outlen, int32_t* status) {
+  ZPQ_TRY
+  if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  (void)make_config(xmethod, args);
+  const int level = args[1] & 3;
+  if (xmethod[0] == '0' || args[1] < 1 || args[1] > 3 || level < 1 || level > 2)
+    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not an LZ77 method of level 1 or 2 without E8E9");
+  std::vector<UnlzJob> jobs;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
+    outlen[i] = 0;
+    status[i] = 1;
+    jobs.push_back(UnlzJob{stream[i], len[i], out[i], cap[i], nullptr});
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
+  std::string note;
+  const int got = engine_lz77_decode((U32)level, lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
+  for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
+  if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+uint32_t zpq_last_device_unlz_segments(void) { return last_device_unlz_segments(); }
+
 int zpq_sha1_batch_device(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out20n) {
   ZPQ_TRY
   if (n && (!in || !len || !out20n)) fail(ZPQ_E_ARG, "null argument");

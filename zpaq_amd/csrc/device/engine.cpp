@@ -1998,6 +1998,88 @@ int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<
   return 1;
 }
 
+// device/lz77_decode_kernel.h for a batch of host streams: one upload, the parse, 12 bytes per stream back, the outputs placed
+// back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.
+int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note) {
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (UnlzJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
+  std::vector<UnlzStream> st(n);
+  uint64_t in_bytes = 0, ntok = 0;
+  for (size_t i = 0; i < n; ++i) {
+    UnlzStream& S = st[i];
+    memset(&S, 0, sizeof(S));
+    S.in_off = in_bytes;
+    S.tok_off = ntok;
+    S.in_len = jobs[i].in_len;
+    S.tok_cap = jobs[i].in_len;                      // a code has at least 8 bits: at most one token per stream byte
+    S.level = level;
+    S.rb = rb;
+    S.min_match = min_match;
+    S.mbits = mbits;
+    in_bytes += ((uint64_t)jobs[i].in_len + 3) & ~3ull;
+    ntok += jobs[i].in_len;
+  }
+  Engine& e = eng();
+  std::lock_guard<std::mutex> g(e.mu);
+  require_ready(e);
+  bind_device(e);
+  wait_in_flight(e);
+  // the arena buffer (idle between batches): tokens, the stream table, the results, where the outputs start
+  const uint64_t o_st = (16 * ntok + 255) & ~255ull;
+  const uint64_t o_res = (o_st + n * sizeof(UnlzStream) + 255) & ~255ull;
+  const uint64_t o_off = (o_res + n * sizeof(UnlzResult) + 255) & ~255ull;
+  const uint64_t ws = o_off + 8 * n + 256;
+  if (ws + in_bytes + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return -1; }
+  e.io_in.ensure(in_bytes + 64);
+  e.arena.ensure(ws);
+  uint8_t* const ab = (uint8_t*)e.arena.p;
+  std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* at = stage.get() + st[i].in_off;
+    if (jobs[i].in_len) memcpy(at, jobs[i].in, jobs[i].in_len);
+    memset(at + jobs[i].in_len, 0, (size_t)((0u - jobs[i].in_len) & 3u));
+  }
+  if (in_bytes) HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), in_bytes, hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), n * sizeof(UnlzStream), hipMemcpyHostToDevice, e.stream));
+  hipError_t rc = launch_unlz_parse((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (UnlzResult*)(ab + o_res), e.stream);
+  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); return -1; }
+  std::vector<UnlzResult> res(n);
+  HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, n * sizeof(UnlzResult), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  std::vector<uint64_t> off(n);
+  uint64_t room = 0;
+  bool fits = true, any = false;
+  for (size_t i = 0; i < n; ++i) {
+    off[i] = room;
+    if (res[i].status != kUnlzOk) continue;
+    jobs[i].out_len = res[i].out_len;
+    room += res[i].out_len;
+    any = true;
+    if (!jobs[i].vec && res[i].out_len > jobs[i].cap) fits = false;
+  }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
+  if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
+  if (!fits) return 0;
+  if (any) {
+    e.io_out.ensure(room + 64);
+    HIP_CHECK(hipMemcpyAsync(ab + o_off, off.data(), 8 * n, hipMemcpyHostToDevice, e.stream));
+    rc = launch_unlz_copy((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (const UnlzResult*)(ab + o_res),
+                          (const uint64_t*)(ab + o_off), (uint8_t*)e.io_out.p, e.stream);
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
+    for (size_t i = 0; i < n; ++i) {
+      if (res[i].status != kUnlzOk) continue;
+      if (jobs[i].vec) jobs[i].vec->resize(res[i].out_len);
+      uint8_t* dst = jobs[i].vec ? jobs[i].vec->data() : jobs[i].out;
+      if (res[i].out_len) HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + off[i], res[i].out_len, hipMemcpyDeviceToHost, e.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+  }
+  for (size_t i = 0; i < n; ++i) if (res[i].status == kUnlzOk) jobs[i].status = 0;
+  return 1;
+}
+
 int engine_jit_threads() { return jit_threads(); }
 
 int engine_selftest(int32_t out[8]) {

@@ -118,6 +118,17 @@ inline bool hash_job_in_range(const SortJob& j) {
 // -1 + note: the device declines (blocks of 2^24 bytes and more, more than 65 535 blocks, 2 GiB per batch, memory).
 struct CodeJob { const U8* data; U32 n, kind, min_match, rb; const LzToken* toks; size_t ntok; };
 int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<U8>>& out, std::string& note);
+// LZ77 streams of one method back into their blocks on the device (device/lz77_decode_kernel.h): what the method's PCOMP program
+// (level 1 / 2 without E8E9; rb = lz_offset_rb, mbits = the program's pm) makes of each stream, or status 1: declined, the output
+// untouched -- the device never gives a verdict on a stream.  The output goes to `vec` (resized) when set, else to out[0..cap).
+// 1: done, status / out_len per job; 0: some decoded block does not fit its cap -- every out_len is reported, nothing is written;
+// -1 + note: the device declines the batch (more than 65 535 streams, 2 GiB of output, memory).
+struct UnlzJob { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
+int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note);
+// Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNLZ is unset: from the smallest batch at which
+// it was faster than both other routes (the translated program on the device, a lane per segment; the host's translated
+// programs) in every alternation of the measurement -- 256 segments of 1 MiB (DESIGN 4.5.3 has the table and the rule).
+inline bool lz_unlz_pays(U64 segments, U64 /*stream_bytes*/) { return segments >= 256; }
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)
 

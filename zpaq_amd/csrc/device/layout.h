@@ -222,6 +222,21 @@ static inline void lz_hash_plan(LzBlock& B, uint64_t& nkeys, uint64_t& nidx) {
   nidx += (1ull << B.idx_bits) + 1u;
 }
 
+// LZ77 streams back into their blocks (device/lz77_decode_kernel.h)
+struct UnlzStream {
+  uint64_t in_off;       // first byte of the stream in the batch's buffer, a multiple of 4
+  uint64_t tok_off;      // first token slot
+  uint32_t in_len;       // bytes
+  uint32_t tok_cap;      // token slots (in_len: a code has at least 8 bits)
+  uint32_t level;        // 1 bit-packed, 2 byte-aligned
+  uint32_t rb;           // level 1: low offset bits written as they are
+  uint32_t min_match;    // level 2
+  uint32_t mbits;        // the program's M holds 2^mbits bytes
+};
+struct UnlzResult { uint32_t out_len, ntok, status; };
+
+enum { kUnlzOk = 0, kUnlzBefore = 1, kUnlzEmpty = 2, kUnlzLong = 3, kUnlzFull = 4, kUnlzField = 5 };
+
 // Cap on HCOMP instructions per input byte: the reference has no limit (a
 // hostile header can loop forever); a device kernel must not hang.
 static const uint32_t kMaxVmSteps = 1u << 20;

@@ -46,4 +46,11 @@ size_t lzc_scan_bytes(uint64_t nslots);
 hipError_t launch_lz77_code_lengths(const LzBlock* blocks, uint32_t nblocks, const LzTok* toks, const uint32_t* counts, const LzCodes& c, hipStream_t st);
 hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, const LzTok* toks, const uint32_t* counts,
                             const LzCodes& c, const uint64_t* out_off, uint8_t* out, hipStream_t st);
+// LZ77 streams back into their blocks (device/lz77_decode_kernel.h): launch_unlz_parse leaves 16-byte tokens (stream b's from
+// toks + streams[b].tok_off, at most tok_cap) and res[b] = {out_len, ntok, status}; the caller reads res, places the outputs --
+// out_off[b] = stream b's first byte in out_all, nstreams words on the device -- and calls launch_unlz_copy, which writes the
+// out_len bytes of every stream whose status is 0 and nothing else.
+hipError_t launch_unlz_parse(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, void* toks, UnlzResult* res, hipStream_t st);
+hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, const void* toks, const UnlzResult* res,
+                            const uint64_t* out_off, uint8_t* out_all, hipStream_t st);
 }  // namespace zpq

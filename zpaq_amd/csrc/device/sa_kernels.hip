@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "lz77_codes_kernel.h"
+#include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
 #include "sa_kernels.h"
@@ -117,6 +118,14 @@ __global__ __launch_bounds__(256) void lzc_match_kernel(const LzBlock* blocks, u
 __global__ __launch_bounds__(256) void lzc_literal_kernel(const uint8_t* in_all, const LzBlock* blocks, uint32_t nblocks, uint64_t total, const LzTok* toks,
                                                           const uint32_t* counts, const uint64_t* pos, const uint64_t* out_off, uint8_t* out) {
   lzc_literal_body(in_all, blocks, nblocks, total, toks, counts, pos, out_off, out);
+}
+
+__global__ __launch_bounds__(64) void unlz_parse_kernel(const uint8_t* in_all, const UnlzStream* streams, uint4* toks, UnlzResult* res) {
+  unlz_parse_body(in_all, streams, toks, res);
+}
+__global__ __launch_bounds__(64) void unlz_copy_kernel(const uint8_t* in_all, const UnlzStream* streams, const uint4* toks, const UnlzResult* res,
+                                                       const uint64_t* out_off, uint8_t* out_all) {
+  unlz_copy_body(in_all, streams, toks, res, out_off, out_all);
 }
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -264,6 +273,23 @@ hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32
   if (total)
     hipLaunchKernelGGL(lzc_literal_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, blocks, nblocks, total, toks, counts, (const uint64_t*)c.pos,
                        out_off, out);
+  return hipGetLastError();
+}
+
+// device/lz77_decode_kernel.h, stage (a): the streams' tokens and {out_len, ntok, status} per stream
+hipError_t launch_unlz_parse(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, void* toks, UnlzResult* res, hipStream_t st) {
+  if (!nstreams) return hipSuccess;
+  if (nstreams > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(unlz_parse_kernel, dim3(nstreams), dim3(64), 0, st, in_all, streams, (uint4*)toks, res);
+  return hipGetLastError();
+}
+
+// stage (c): the outputs, stream b's at out_all + out_off[b]
+hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, const void* toks, const UnlzResult* res,
+                            const uint64_t* out_off, uint8_t* out_all, hipStream_t st) {
+  if (!nstreams) return hipSuccess;
+  if (nstreams > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(unlz_copy_kernel, dim3(nstreams), dim3(64), 0, st, in_all, streams, (const uint4*)toks, res, out_off, out_all);
   return hipGetLastError();
 }
 

@@ -523,7 +523,51 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
   return out;
 }
 
+namespace {
+std::atomic<U32> g_last_unlz_segments{0};
+
+// A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
+// generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
+// args[0] is pm - 20; level 2's minimum match is read where two generated programs differ, then confirmed by the whole comparison.
+struct UnlzProgram { U32 level, rb, min_match, mbits; };
+bool unlz_generated(int a0, const std::string& body, std::vector<U8>& key) {
+  try {
+    int args[9];
+    const std::string cfg = make_config("x" + std::to_string(a0) + body, args);
+    const Assembled as = assemble(cfg.c_str(), args);
+    if (as.pcomp.size() < 3 || as.hcomp.size() < 6) return false;
+    key.assign(as.hcomp.begin() + 4, as.hcomp.begin() + 6);
+    key.insert(key.end(), as.pcomp.begin() + 2, as.pcomp.end());
+    return true;
+  } catch (const std::exception&) { return false; }
+}
+bool unlz_program(const std::vector<U8>& key, UnlzProgram& u) {
+  if (key.size() < 3) return false;
+  const int a0 = (int)key[1] - 20;
+  if (key[0] != 0 || a0 < 0 || a0 > 11) return false;
+  std::vector<U8> k1, k2;
+  if (unlz_generated(a0, ",1", k1) && k1 == key) { u = UnlzProgram{1u, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
+  if (!unlz_generated(a0, ",2,1", k1) || !unlz_generated(a0, ",2,2", k2) || k1.size() != key.size() || k2.size() != key.size()) return false;
+  size_t at = key.size(), differ = 0;
+  for (size_t i = 0; i < key.size(); ++i) if (k1[i] != k2[i]) { at = i; ++differ; }
+  if (differ != 1) return false;
+  const U32 mm = key[at];
+  if (!unlz_generated(a0, ",2," + std::to_string(mm), k1) || k1 != key) return false;
+  u = UnlzProgram{2u, 0u, mm, (U32)key[1]};
+  return true;
+}
+// ZPAQ_AMD_DEVICE_UNLZ: 0 never, 1 always, unset (2): when lz_unlz_pays says so (device/engine.hpp)
+int device_unlz_mode() {
+  const char* v = getenv("ZPAQ_AMD_DEVICE_UNLZ");
+  if (!v || !*v) return 2;
+  return v[0] == '0' ? 0 : 1;
+}
+}  // namespace
+
+U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_order_relaxed); }
+
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
+  g_last_unlz_segments.store(0, std::memory_order_relaxed);
   struct Seg {
     FoundSegment fs;
     zpq_plan* plan = nullptr;     // null: stored block
@@ -647,8 +691,40 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
     }
     size_t nprog = 0;
     for (auto& kv : by_prog) nprog += kv.second.size();
+    // The LZ77 inverses without E8E9 have a decoder of their own on the device (device/lz77_decode_kernel.h: a wavefront per
+    // segment, not a lane): a group of such segments goes there first when no route is forced -- ZPAQ_AMD_DEVICE_UNLZ=0|1 forces
+    // it off or on, unset follows lz_unlz_pays.  Segments it declines stay in their group and go on exactly as before.
+    const int unlz = mode ? 0 : device_unlz_mode();
+    if (unlz && nprog && engine_device_count() > 0) {
+      U32 taken = 0;
+      for (auto& kv : by_prog) {
+        const std::vector<U8>& key = kv.first;
+        UnlzProgram u;
+        if (!unlz_program(key, u)) continue;
+        const size_t skip = 3 + (key.size() - 2);
+        U64 bytes = 0;
+        std::vector<UnlzJob> uj;
+        for (size_t i : kv.second) {
+          const Seg& s = *segs[i];
+          uj.push_back(UnlzJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
+          bytes += s.decoded.size() - skip;
+        }
+        if (unlz != 1 && !lz_unlz_pays(uj.size(), bytes)) continue;
+        std::string note;
+        if (engine_lz77_decode(u.level, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
+        std::vector<size_t> left;
+        for (size_t k = 0; k < uj.size(); ++k) {
+          const size_t i = kv.second[k];
+          if (uj[k].status == 0) { on_device[i] = 1; ++taken; }
+          else { done[i].clear(); left.push_back(i); }
+        }
+        kv.second.swap(left);
+      }
+      g_last_unlz_segments.store(taken, std::memory_order_relaxed);
+    }
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
       for (auto& kv : by_prog) {
+        if (kv.second.empty()) continue;
         const std::vector<U8>& key = kv.first;
         std::vector<PcompSeg> ps;
         for (size_t i : kv.second) {

@@ -59,6 +59,9 @@ std::vector<U8> decode_payload(const std::vector<U8>& header, const U8* payload,
 // receives each segment's post-processed data in order.
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink);
 
+// segments of this process's last decode_archive call that device/lz77_decode_kernel.h decoded
+U32 last_device_unlz_segments();
+
 // PostProcessor (libzpaq.cpp:2183-2241) of one block: the first segment's decoded bytes start with the PP header
 // (0 = PASS, or 1 len16 PCOMP program); every later segment of the block continues in the same mode -- PASS copies,
 // PROG feeds the same ZPAQL machine -- and each segment ends with the machine's EOS call.
