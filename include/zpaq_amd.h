@@ -353,6 +353,27 @@ int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, co
  * groups of 256 segments and more, the smallest batch at which it was faster than both other routes.  Any set
  * value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  The bytes are the same either way. */
 uint32_t zpq_last_device_unlz_segments(void);
+/* The same for a batch of BWT streams (level 3 without E8E9, args[0] <= 4: x0,3 .. x4,3) on the device
+ * (device/bwt_decode_kernel.h: a stable counting sort per tile, then the list ranked from every 256th node at once).  A stream
+ * is S[0 .. n] and idx in 4 bytes, low byte first.  status[b]: 0 decoded -- out[b] holds, byte for byte, what
+ * zpq_postprocess_block makes of stream b, outlen[b] its size (ff 00 00 00 00, the empty block, decodes to nothing); 1 declined
+ * -- out[b] is untouched, outlen[b] is 0 and the caller runs the program on the host: a stream shorter than 5 bytes or outside
+ * the rule 1 <= idx <= n and S[idx] == 255, n >= 2^24, n + 257 > 2^(args[0] + 20) (the program's counters would not fit), a
+ * list whose path from idx has not exactly n nodes.  The device never gives a verdict on a damaged stream, and it declines no
+ * stream this library's BWT writes.  Sizes are known before anything runs (n = len - 5): when an admitted stream does not fit
+ * its buffer every size is reported and nothing is launched (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED with a note in zpq_last_error
+ * without a device, for another kind of method, or outside the range (65 535 streams and 2 GiB of output per batch; 4 bytes of
+ * workspace per stream byte, the tile histograms, the splitter tables and the outputs within the device budget). */
+int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                          uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that device/bwt_decode_kernel.h decoded.  A segment qualifies when its
+ * block has one segment and carries, byte for byte, the BWT program without E8E9 that compressBlock's methods generate at
+ * args[0] <= 4 (the BWT branches of methods 3 and 4, x.,3..) with ph = pm = args[0] + 20; E8E9 variants, args[0] > 4, custom
+ * programs and blocks of several segments never do.  ZPAQ_AMD_DEVICE_UNBWT=0|1 forces the route off or on for qualifying
+ * segments; unset it is off: it is taken only from a measured group size of 64 segments or more at which it beat both other
+ * routes, and no measurement exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.
+ * The bytes are the same either way. */
+uint32_t zpq_last_device_unbwt_segments(void);
 void zpq_e8e9(uint8_t* data, uint32_t n);      /* e8e9 (libzpaq.cpp:6450-6459), in place */
 /* Compiler alone (libzpaq.cpp:2698): ZPAQL source text -> header / PCOMP bytes. */
 int zpq_assemble(const char* config, const int* args9, uint8_t* hcomp, size_t hcap,

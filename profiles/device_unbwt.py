@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Where the BWT streams of an archive should be decoded: end-to-end zpq_decompress time with the device's BWT decoder
+(ZPAQ_AMD_DEVICE_UNBWT=1: device/bwt_decode_kernel.h, a counting sort per tile and the list ranked from every 256th node), with
+the route decompression had before it (ZPAQ_AMD_DEVICE_UNBWT=0: the translated PCOMP program on the device, a lane per segment,
+from 4 segments or 256 KiB on -- the yardstick) and with the host's translated programs (ZPAQ_AMD_PCOMP=host), by a host clock
+around the call, after one warm-up call per setting, the settings alternating `--reps` times in one process.  DESIGN 4.5.4 has
+the table this prints.
+
+    python profiles/device_unbwt.py [--cases CASE ...] [--reps 3] [--settings unbwt1,unbwt0,host] [--out FILE]
+
+Cases: <method>:<kind>:<block bytes>:<blocks>.  Inputs: up to 64 distinct blocks of zpaq_amd.corpus, repeated to the count asked
+for, compressed once with zpq_compress_blocks.  The output of every call is compared with the input.  Per case: the calls'
+milliseconds, MB/s of the best call, the segments the new kernels decoded, and whether the new route was faster than both others
+in every alternation -- the rule behind bwt_unbwt_pays (device/engine.hpp).
+
+For kernel times run this under rocprofv3 --kernel-trace --stats in a run of its own."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BLOCK = (1 << 20) - 4096                                     # the largest block an x0 method compresses (the program would hold 2^20 - 257)
+DEFAULT_CASES = (
+    [f"x0,3:text:{BLOCK}:{nb}" for nb in (4, 64, 256, 1024)]  # no model behind the BWT: the stage alone
+    + [f"x0,3:zeros:{BLOCK}:256", f"x0,3:records:{BLOCK}:256", f"x0,3:lcg:{BLOCK}:256"]
+    + [f"x0,3ci1:text:{BLOCK}:64"]                            # a model behind it: its decode is in the call
+)
+SETTINGS = {
+    "unbwt1": {"ZPAQ_AMD_DEVICE_UNBWT": "1"},
+    "unbwt0": {"ZPAQ_AMD_DEVICE_UNBWT": "0"},
+    "host": {"ZPAQ_AMD_PCOMP": "host"},
+}
+u8p = C.POINTER(C.c_ubyte)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="*", default=DEFAULT_CASES)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--settings", default="unbwt1,unbwt0,host")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import zpaq_amd as z
+    from zpaq_amd import corpus
+    L = z.lib()
+    z.init(0)
+    settings = tuple(a.settings.split(","))
+    rows = []
+    for case in a.cases:
+        method, kind, nbytes, nb = case.split(":")
+        nbytes, nb = int(nbytes), int(nb)
+        distinct = [corpus.block(kind, nbytes, 7000 + i) for i in range(min(nb, 64))]
+        arch = z.compress_blocks([d.copy() for d in distinct], method)
+        archive = np.frombuffer(b"".join(arch[i % len(arch)] for i in range(nb)), np.uint8)
+        want = np.concatenate([distinct[i % len(distinct)] for i in range(nb)])
+        out = np.empty(want.size + 64, np.uint8)
+        ol = C.c_uint64(0)
+
+        def call(name):
+            for k in ("ZPAQ_AMD_DEVICE_UNBWT", "ZPAQ_AMD_PCOMP"):
+                os.environ.pop(k, None)
+            os.environ.update(SETTINGS[name])
+            t0 = time.perf_counter()
+            rc = L.zpq_decompress(archive.ctypes.data_as(u8p), archive.size, out.ctypes.data_as(u8p), out.size, C.byref(ol))
+            dt = time.perf_counter() - t0
+            assert rc == 0, (case, name, L.zpq_last_error())
+            assert ol.value == want.size and np.array_equal(out[:want.size], want), (case, name, "the output is not the input")
+            return dt, int(L.zpq_last_device_unbwt_segments())
+
+        for s in settings:                                     # warm-up: buffers, pinned staging, code objects
+            call(s)
+        times = {s: [] for s in settings}
+        segs = {}
+        for _ in range(a.reps):
+            for s in settings:
+                dt, n = call(s)
+                times[s].append(round(dt * 1e3, 2))
+                segs[s] = n
+        new, others = settings[0], settings[1:]
+        row = {"method": method, "kind": kind, "block_bytes": nbytes, "blocks": nb, "archive_bytes": int(archive.size), "ms": times,
+               "mb_per_s": {s: round(nbytes * nb / 1e6 / (min(times[s]) / 1e3), 1) for s in settings}, "device_unbwt_segments": segs,
+               "faster_than_both_in_every_alternation": all(all(x < y for x, y in zip(times[new], times[o])) for o in others)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        if a.out:
+            with open(a.out, "w") as fh:
+                json.dump(rows, fh, indent=1)
+    L.zpq_shutdown()
+
+
+if __name__ == "__main__":
+    main()

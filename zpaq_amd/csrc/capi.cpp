@@ -641,6 +641,35 @@ int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_unlz_segments(void) { return last_device_unlz_segments(); }
 
+// ... and for a batch of BWT streams on the device (device/bwt_decode_kernel.h)
+int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                          size_t* outlen, int32_t* status) {
+  ZPQ_TRY
+  if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  (void)make_config(xmethod, args);
+  if (xmethod[0] == '0' || args[1] != 3 || args[0] > 4)
+    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not a BWT method (level 3) without E8E9 at args[0] <= 4");
+  std::vector<UnbwtJob> jobs;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
+    outlen[i] = 0;
+    status[i] = 1;
+    jobs.push_back(UnbwtJob{stream[i], len[i], out[i], cap[i], nullptr});
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
+  std::string note;
+  const int got = engine_bwt_decode((U32)(args[0] + 20), jobs, note);
+  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
+  for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
+  if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+uint32_t zpq_last_device_unbwt_segments(void) { return last_device_unbwt_segments(); }
+
 int zpq_sha1_batch_device(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out20n) {
   ZPQ_TRY
   if (n && (!in || !len || !out20n)) fail(ZPQ_E_ARG, "null argument");

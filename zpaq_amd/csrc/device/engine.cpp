@@ -2080,6 +2080,89 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
   return 1;
 }
 
+// device/bwt_decode_kernel.h for a batch of host streams.  The host admits the streams (the rule, the range), so every size is
+// known and the room is checked before anything runs; then one upload, the six kernels, a word per stream back, and the outputs
+// of the streams whose path was whole down.
+int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note) {
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (UnbwtJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
+  std::vector<BwtStream> st;
+  std::vector<size_t> who;                          // st[k] is jobs[who[k]]
+  std::vector<char> empty(n, 0);
+  uint64_t in_bytes = 0, nodes = 0, tiles = 0, splits = 0, room = 0;
+  bool fits = true;
+  for (size_t i = 0; i < n; ++i) {
+    const UnbwtJob& j = jobs[i];
+    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
+    BwtStream S;
+    memset(&S, 0, sizeof(S));
+    if (!bwt_stream_admitted(j.in, j.in_len, mbits, S.n, S.idx)) continue;
+    S.in_off = in_bytes;
+    S.link_off = nodes;
+    S.out_off = room;
+    S.tile_off = (uint32_t)tiles;
+    S.sp_off = (uint32_t)splits;
+    in_bytes += ((uint64_t)j.in_len + 3) & ~3ull;
+    nodes += (uint64_t)S.n + 1;
+    tiles += bwt_tiles(S.n);
+    splits += bwt_splitters(S.n);
+    room += S.n;
+    jobs[i].out_len = S.n;
+    if (!j.vec && S.n > j.cap) fits = false;
+    st.push_back(S);
+    who.push_back(i);
+  }
+  const size_t m = st.size();
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+  if (!fits) return 0;
+  if (m) {
+    Engine& e = eng();
+    std::lock_guard<std::mutex> g(e.mu);
+    require_ready(e);
+    bind_device(e);
+    wait_in_flight(e);
+    // the arena buffer (idle between batches): the list, the tile histograms, the splitters, the stream table, the statuses
+    const uint64_t o_hist = (4 * nodes + 255) & ~255ull;
+    const uint64_t o_sp = (o_hist + 1024 * tiles + 255) & ~255ull;
+    const uint64_t o_st = (o_sp + 16 * splits + 255) & ~255ull;
+    const uint64_t o_res = (o_st + m * sizeof(BwtStream) + 255) & ~255ull;
+    const uint64_t ws = o_res + 4 * m + 256;
+    if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+    e.io_in.ensure(in_bytes + 64);
+    e.io_out.ensure(room + 64);
+    e.arena.ensure(ws);
+    uint8_t* const ab = (uint8_t*)e.arena.p;
+    std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
+    for (size_t k = 0; k < m; ++k) {
+      const UnbwtJob& j = jobs[who[k]];
+      uint8_t* at = stage.get() + st[k].in_off;
+      memcpy(at, j.in, j.in_len);
+      memset(at + j.in_len, 0, (size_t)((0u - j.in_len) & 3u));
+    }
+    HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), in_bytes, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
+    const hipError_t rc = launch_bwt_decode((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (uint32_t)m, (uint32_t)tiles, (uint32_t)splits,
+                                            (uint32_t*)(ab + o_hist), (uint32_t*)ab, ab + o_sp, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device BWT decoder failed: ") + hipGetErrorString(rc); for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+    std::vector<uint32_t> res(m);
+    HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    for (size_t k = 0; k < m; ++k) {
+      UnbwtJob& j = jobs[who[k]];
+      if (res[k] != 0) { j.out_len = 0; continue; }
+      if (j.vec) j.vec->resize(st[k].n);
+      uint8_t* dst = j.vec ? j.vec->data() : j.out;
+      HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + st[k].out_off, st[k].n, hipMemcpyDeviceToHost, e.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
+  }
+  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
+  return 1;
+}
+
 int engine_jit_threads() { return jit_threads(); }
 
 int engine_selftest(int32_t out[8]) {

@@ -129,6 +129,19 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
 // it was faster than both other routes (the translated program on the device, a lane per segment; the host's translated
 // programs) in every alternation of the measurement -- 256 segments of 1 MiB (DESIGN 4.5.3 has the table and the rule).
 inline bool lz_unlz_pays(U64 segments, U64 /*stream_bytes*/) { return segments >= 256; }
+// BWT streams back into their blocks on the device (device/bwt_decode_kernel.h): what the program of a BWT method without E8E9
+// at args[0] <= 4 (mbits = the program's pm = ph) makes of each stream, or status 1: declined, the output untouched -- a stream
+// outside the rule 1 <= idx <= n, S[idx] == 255 or shorter than 5 bytes, n >= 2^24, n + 257 > 2^mbits, a path that has not n
+// nodes.  The device never gives a verdict on a stream.  Sizes are known before any kernel runs (n = in_len - 5), so:
+// 1: done, status / out_len per job; 0: some admitted stream does not fit its cap -- every out_len is reported, nothing is
+// launched or written; -1 + note: the device declines the batch (more than 65 535 streams, 2 GiB of output, memory: 4 bytes per
+// stream byte, the tile histograms, the splitter tables and the outputs count against the engine's budget).
+struct UnbwtJob { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
+int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note);
+// Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNBWT is unset.  The rule is the one of
+// lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
+// all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
+inline bool bwt_unbwt_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)
 

@@ -237,6 +237,38 @@ struct UnlzResult { uint32_t out_len, ntok, status; };
 
 enum { kUnlzOk = 0, kUnlzBefore = 1, kUnlzEmpty = 2, kUnlzLong = 3, kUnlzFull = 4, kUnlzField = 5 };
 
+// BWT streams back into their blocks (device/bwt_decode_kernel.h).  A stream is S[0 .. n] and idx in 4 bytes, low byte first.
+enum { kBwtTile = 4096, kBwtChunk = 64, kBwtStride = 256 };      // bytes per tile of the counting sort, per step of it, nodes per splitter
+struct BwtStream {
+  uint64_t in_off;       // S[0] in the batch's buffer, a multiple of 4
+  uint64_t link_off;     // the word of node 0 (n + 1 words)
+  uint64_t out_off;      // first byte of the output (n bytes, back to back with its neighbours)
+  uint32_t n;            // bytes of the block, at least 1
+  uint32_t idx;          // 1 .. n, S[idx] == 255: the marker, which is no byte of the block
+  uint32_t tile_off;     // first tile: (n + 1 + kBwtTile - 1) / kBwtTile of them, 256 words each
+  uint32_t sp_off;       // first splitter: n / kBwtStride + 2 of them (entry 0: node 0, the end; the last: the head, node idx)
+};
+// what a stream needs of each array (the engine and the emulator's driver place a batch with this)
+static inline uint32_t bwt_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + 1u + kBwtTile - 1u) / kBwtTile); }
+static inline uint32_t bwt_splitters(uint32_t n) { return n / kBwtStride + 2u; }
+// Whether the device takes a stream at all -- everything else is declined before any kernel runs: the rule 1 <= idx <= n and
+// S[idx] == 255 (outside it the program's counts and links disagree), n < 2^24 (the node rides in 24 bits of the list's word),
+// n + 257 <= 2^mbits (the program's 256 counters sit at the top of H).
+static inline bool bwt_stream_admitted(const uint8_t* s, uint64_t len, uint32_t mbits, uint32_t& n, uint32_t& idx) {
+  if (len < 6 || len - 5 >= (1ull << 24) || mbits > 32u) return false;
+  const uint64_t n64 = len - 5;
+  if (n64 + 257u > (1ull << mbits)) return false;
+  const uint8_t* t = s + n64 + 1;
+  const uint32_t i = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+  if (i < 1u || i > n64 || s[i] != 255u) return false;
+  n = (uint32_t)n64;
+  idx = i;
+  return true;
+}
+static inline bool bwt_stream_empty(const uint8_t* s, uint64_t len) {      // what preprocess_block writes for an empty block
+  return len == 5 && s[0] == 255u && !s[1] && !s[2] && !s[3] && !s[4];
+}
+
 // Cap on HCOMP instructions per input byte: the reference has no limit (a
 // hostile header can loop forever); a device kernel must not hang.
 static const uint32_t kMaxVmSteps = 1u << 20;

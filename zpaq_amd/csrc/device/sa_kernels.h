@@ -53,4 +53,10 @@ hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32
 hipError_t launch_unlz_parse(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, void* toks, UnlzResult* res, hipStream_t st);
 hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, const void* toks, const UnlzResult* res,
                             const uint64_t* out_off, uint8_t* out_all, hipStream_t st);
+// BWT streams back into their blocks (device/bwt_decode_kernel.h): count, scan, link, rank, offsets and emit for nstreams
+// admitted streams (layout.h bwt_stream_admitted) placed as `streams` says -- ntiles tiles of 256 words in hist, a word per node
+// in link, nsplit entries of 16 bytes in splitters.  status[b] = 0: out_all + out_off holds stream b's n bytes; 1: its path has
+// not n nodes and nothing of it was written.
+hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t ntiles, uint32_t nsplit, uint32_t* hist,
+                             uint32_t* link, void* splitters, uint32_t* status, uint8_t* out_all, hipStream_t st);
 }  // namespace zpq

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "bwt_decode_kernel.h"
 #include "lz77_codes_kernel.h"
 #include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
@@ -126,6 +127,23 @@ __global__ __launch_bounds__(64) void unlz_parse_kernel(const uint8_t* in_all, c
 __global__ __launch_bounds__(64) void unlz_copy_kernel(const uint8_t* in_all, const UnlzStream* streams, const uint4* toks, const UnlzResult* res,
                                                        const uint64_t* out_off, uint8_t* out_all) {
   unlz_copy_body(in_all, streams, toks, res, out_off, out_all);
+}
+
+__global__ __launch_bounds__(64) void unbwt_count_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t* hist) {
+  unbwt_count_body(in_all, streams, nstreams, hist);
+}
+__global__ __launch_bounds__(256) void unbwt_scan_kernel(const BwtStream* streams, uint32_t* hist) { unbwt_scan_body(streams, hist); }
+__global__ __launch_bounds__(64) void unbwt_link_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
+                                                      uint32_t* link) {
+  unbwt_link_body(in_all, streams, nstreams, hist, link);
+}
+__global__ __launch_bounds__(256) void unbwt_rank_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link, uint4* sp) {
+  unbwt_rank_body(streams, nstreams, nsplit, link, sp);
+}
+__global__ __launch_bounds__(64) void unbwt_offsets_kernel(const BwtStream* streams, uint4* sp, uint32_t* status) { unbwt_offsets_body(streams, sp, status); }
+__global__ __launch_bounds__(256) void unbwt_emit_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link, const uint4* sp,
+                                                         const uint32_t* status, uint8_t* out_all) {
+  unbwt_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
 }
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -290,6 +308,23 @@ hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, ui
   if (!nstreams) return hipSuccess;
   if (nstreams > 65535u) return hipErrorInvalidValue;
   hipLaunchKernelGGL(unlz_copy_kernel, dim3(nstreams), dim3(64), 0, st, in_all, streams, (const uint4*)toks, res, out_off, out_all);
+  return hipGetLastError();
+}
+
+// device/bwt_decode_kernel.h: the six stages for a batch of admitted streams, one after the other on `st`
+hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t ntiles, uint32_t nsplit, uint32_t* hist,
+                             uint32_t* link, void* splitters, uint32_t* status, uint8_t* out_all, hipStream_t st) {
+  if (!nstreams) return hipSuccess;
+  if (nstreams > 65535u || !ntiles || !nsplit) return hipErrorInvalidValue;
+  uint4* sp = (uint4*)splitters;
+  const uint32_t spb = (nsplit + 255u) / 256u;
+  hipLaunchKernelGGL(unbwt_count_kernel, dim3(ntiles), dim3(64), 0, st, in_all, streams, nstreams, hist);
+  hipLaunchKernelGGL(unbwt_scan_kernel, dim3(nstreams), dim3(256), 0, st, streams, hist);
+  hipLaunchKernelGGL(unbwt_link_kernel, dim3(ntiles), dim3(64), 0, st, in_all, streams, nstreams, (const uint32_t*)hist, link);
+  hipLaunchKernelGGL(unbwt_rank_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint32_t*)link, sp);
+  hipLaunchKernelGGL(unbwt_offsets_kernel, dim3(nstreams), dim3(64), 0, st, streams, sp, status);
+  hipLaunchKernelGGL(unbwt_emit_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint32_t*)link, (const uint4*)sp,
+                     (const uint32_t*)status, out_all);
   return hipGetLastError();
 }
 

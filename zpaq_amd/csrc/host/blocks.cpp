@@ -524,7 +524,7 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
 }
 
 namespace {
-std::atomic<U32> g_last_unlz_segments{0};
+std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0};
 
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
@@ -562,12 +562,31 @@ int device_unlz_mode() {
   if (!v || !*v) return 2;
   return v[0] == '0' ? 0 : 1;
 }
+// The inverse BWT without E8E9 at args[0] <= 4 (pcomp_bwt(arg0, false): the byte rides in the list's word), recognised the same
+// way; ph and pm are both args[0] + 20.
+bool unbwt_program(const std::vector<U8>& key, U32& mbits) {
+  if (key.size() < 3 || key[0] != key[1]) return false;
+  const int a0 = (int)key[1] - 20;
+  if (a0 < 0 || a0 > 4) return false;
+  std::vector<U8> k;
+  if (!unlz_generated(a0, ",3", k) || k != key) return false;
+  mbits = key[1];
+  return true;
+}
+// ZPAQ_AMD_DEVICE_UNBWT: 0 never, 1 always, unset (2): when bwt_unbwt_pays says so (device/engine.hpp)
+int device_unbwt_mode() {
+  const char* v = getenv("ZPAQ_AMD_DEVICE_UNBWT");
+  if (!v || !*v) return 2;
+  return v[0] == '0' ? 0 : 1;
+}
 }  // namespace
 
 U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_order_relaxed); }
+U32 last_device_unbwt_segments() { return g_last_unbwt_segments.load(std::memory_order_relaxed); }
 
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
   g_last_unlz_segments.store(0, std::memory_order_relaxed);
+  g_last_unbwt_segments.store(0, std::memory_order_relaxed);
   struct Seg {
     FoundSegment fs;
     zpq_plan* plan = nullptr;     // null: stored block
@@ -721,6 +740,36 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
         kv.second.swap(left);
       }
       g_last_unlz_segments.store(taken, std::memory_order_relaxed);
+    }
+    // The inverse BWT without E8E9 likewise (device/bwt_decode_kernel.h: a counting sort per tile, the list ranked from every
+    // 256th node at once): ZPAQ_AMD_DEVICE_UNBWT=0|1 forces it off or on, unset follows bwt_unbwt_pays.
+    const int unbwt = mode ? 0 : device_unbwt_mode();
+    if (unbwt && nprog && engine_device_count() > 0) {
+      U32 taken = 0;
+      for (auto& kv : by_prog) {
+        const std::vector<U8>& key = kv.first;
+        U32 mbits = 0;
+        if (kv.second.empty() || !unbwt_program(key, mbits)) continue;
+        const size_t skip = 3 + (key.size() - 2);
+        U64 bytes = 0;
+        std::vector<UnbwtJob> uj;
+        for (size_t i : kv.second) {
+          const Seg& s = *segs[i];
+          uj.push_back(UnbwtJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
+          bytes += s.decoded.size() - skip;
+        }
+        if (unbwt != 1 && !bwt_unbwt_pays(uj.size(), bytes)) continue;
+        std::string note;
+        if (engine_bwt_decode(mbits, uj, note) != 1) continue;
+        std::vector<size_t> left;
+        for (size_t k = 0; k < uj.size(); ++k) {
+          const size_t i = kv.second[k];
+          if (uj[k].status == 0) { on_device[i] = 1; ++taken; }
+          else { done[i].clear(); left.push_back(i); }
+        }
+        kv.second.swap(left);
+      }
+      g_last_unbwt_segments.store(taken, std::memory_order_relaxed);
     }
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
       for (auto& kv : by_prog) {

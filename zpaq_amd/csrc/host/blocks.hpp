@@ -61,6 +61,8 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
 
 // segments of this process's last decode_archive call that device/lz77_decode_kernel.h decoded
 U32 last_device_unlz_segments();
+// ... that device/bwt_decode_kernel.h decoded
+U32 last_device_unbwt_segments();
 
 // PostProcessor (libzpaq.cpp:2183-2241) of one block: the first segment's decoded bytes start with the PP header
 // (0 = PASS, or 1 len16 PCOMP program); every later segment of the block continues in the same mode -- PASS copies,
