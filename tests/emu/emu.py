@@ -299,7 +299,8 @@ def build_lz77() -> str:
     import zpaq_amd as z
     dev = os.path.join(ROOT, "zpaq_amd", "csrc", "device")
     srcs = (os.path.join(EMU, "wave_emu.h"), os.path.join(EMU, "wave_emu.cpp"), os.path.join(EMU, "lz77_emu_main.cpp"),
-            os.path.join(dev, "lz77_kernel.h"), os.path.join(dev, "layout.h"))
+            os.path.join(EMU, "sa_emu.h"), os.path.join(EMU, "guard_alloc.h"),
+            os.path.join(dev, "lz77_kernel.h"), os.path.join(dev, "sa_kernel.h"), os.path.join(dev, "layout.h"))
     flags = _sanitize_flags()
     key = hashlib.sha1(b"".join(open(p, "rb").read() for p in srcs) + " ".join(flags).encode()).hexdigest()[:20]
     os.makedirs(BUILD, exist_ok=True)
@@ -316,9 +317,10 @@ def build_lz77() -> str:
     return exe
 
 
-def lz77_run(kind: int, min_match: int, lookahead: int, bucket: int, checkbits: int, inputs: Sequence[bytes]):
+def lz77_run(kind: int, min_match: int, lookahead: int, bucket: int, checkbits: int, inputs: Sequence[bytes], emulated_sort: bool = False):
     """device/lz77_kernel.h on the emulator: per input the token list (kind 1 / 2: 16 bytes per match) or the BWT stream
-    (kind 3: n + 5 bytes) the device would hand back."""
+    (kind 3: n + 5 bytes) the device would hand back.  emulated_sort: the suffix arrays and ranks come from the emulated sort
+    of the whole batch (device/sa_kernel.h) instead of the host's sorter."""
     exe = build_lz77()
     with tempfile.TemporaryDirectory() as td:
         paths = []
@@ -328,8 +330,73 @@ def lz77_run(kind: int, min_match: int, lookahead: int, bucket: int, checkbits: 
                 fh.write(bytes(data))
             paths.append(pth)
         prefix = os.path.join(td, "out")
-        r = subprocess.run([exe, str(kind), str(min_match), str(lookahead), str(bucket), str(checkbits), prefix, *paths],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        r = subprocess.run([exe, *(["--emulated-sort"] if emulated_sort else []), str(kind), str(min_match), str(lookahead), str(bucket), str(checkbits),
+                            prefix, *paths], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"lz77 emulator failed ({r.returncode}):\n" + r.stdout[-4000:])
         return [open(f"{prefix}.{k}", "rb").read() for k in range(len(inputs))]
+
+
+def build_sa() -> str:
+    """The emulator executable of the batched suffix sort (device/sa_kernel.h through tests/emu/sa_emu_main.cpp)."""
+    dev = os.path.join(ROOT, "zpaq_amd", "csrc", "device")
+    srcs = (os.path.join(EMU, "wave_emu.h"), os.path.join(EMU, "wave_emu.cpp"), os.path.join(EMU, "sa_emu_main.cpp"), os.path.join(EMU, "sa_emu.h"),
+            os.path.join(EMU, "guard_alloc.h"), os.path.join(dev, "sa_kernel.h"))
+    flags = _sanitize_flags()
+    key = hashlib.sha1(b"".join(open(p, "rb").read() for p in srcs) + " ".join(flags).encode()).hexdigest()[:20]
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, f"sa_{key}")
+    if os.path.exists(exe):
+        return exe
+    tmp = f"{exe}.{os.getpid()}.tmp"
+    cmd = ["g++", "-O1", "-std=c++17", "-w", *flags, "-I", EMU, "-I", dev, os.path.join(EMU, "sa_emu_main.cpp"), os.path.join(EMU, "wave_emu.cpp"), "-o", tmp]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("suffix sort emulator build failed:\n" + r.stdout[-6000:])
+    os.replace(tmp, exe)
+    return exe
+
+
+def sa_run_batches(batches: Sequence[Sequence[bytes]], names: Sequence[str] | None = None):
+    """Every batch through the emulated sort, all in one process: per batch ([suffix array per input], [final rank array per
+    input], rounds), the arrays as numpy uint32.  A guard page hit or a loop that does not end raises, naming the batch."""
+    import numpy as np
+    exe = build_sa()
+    with tempfile.TemporaryDirectory() as td:
+        argv = []
+        for t, inputs in enumerate(batches):
+            if not inputs:
+                raise ValueError("a batch needs at least one input")
+            if t:
+                argv.append("--")
+            for k, data in enumerate(inputs):
+                pth = os.path.join(td, f"in{t}.{k}")
+                with open(pth, "wb") as fh:
+                    fh.write(bytes(data))
+                argv.append(pth)
+        prefix = os.path.join(td, "out")
+        r = subprocess.run([exe, "sort", prefix, *argv], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1800)
+        if r.returncode != 0:
+            at = sum(1 for l in r.stdout.splitlines() if l.startswith("batch "))
+            raise RuntimeError(f"suffix sort emulator failed ({r.returncode}) in batch {at}" + (f" ({names[at]})" if names and at < len(names) else "") +
+                               ":\n" + r.stdout[-1000:])
+        rounds = {int(l.split()[1]): int(l.split()[5]) for l in r.stdout.splitlines() if l.startswith("batch ")}
+        res = []
+        for t, inputs in enumerate(batches):
+            sa = [np.fromfile(f"{prefix}.{t}.{k}.sa", "<u4") for k in range(len(inputs))]
+            rank = [np.fromfile(f"{prefix}.{t}.{k}.rank", "<u4") for k in range(len(inputs))]
+            res.append((sa, rank, rounds[t]))
+        return res
+
+
+def sa_run(inputs: Sequence[bytes]):
+    """One batch through the emulated sort: ([suffix array per input], [final rank array per input], rounds)."""
+    return sa_run_batches([inputs])[0]
+
+
+def sa_helper(*words) -> int:
+    """The loop's decisions as device/sa_kernel.h makes them: sa_helper("bits", nblocks), sa_helper("stop", names, total, h, max_len)."""
+    r = subprocess.run([build_sa(), *[str(w) for w in words]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"suffix sort emulator failed ({r.returncode}):\n" + r.stdout[-4000:])
+    return int(r.stdout.split()[1])

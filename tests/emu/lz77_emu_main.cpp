@@ -1,17 +1,20 @@
 // TEST INFRASTRUCTURE -- the pre-processor kernels behind the suffix sort (zpaq_amd/csrc/device/lz77_kernel.h) on the
 // host-side wavefront emulator (wave_emu.h), against the host's own parse.
 //
-//   lz77_emu <kind> <min_match> <lookahead> <bucket> <checkbits> <out_prefix> <input> [<input> ...]
+//   lz77_emu [--emulated-sort] <kind> <min_match> <lookahead> <bucket> <checkbits> <out_prefix> <input> [<input> ...]
 //
 // kind 1 / 2: LZ77 (bit-packed / byte-aligned codes) -> <out_prefix>.<k> = block k's token list (16 bytes per match);
 // kind 3: BWT -> <out_prefix>.<k> = the n + 5 bytes preprocess_block makes.  The suffix array comes from the library's host
-// sorter (zpq_suffix_array_host), the rank array is its inverse + 1: what device/sa_kernels.hip leaves behind.
+// sorter (zpq_suffix_array_host), the rank array is its inverse + 1: what device/sa_kernels.hip leaves behind -- which
+// tests/test_emu_sa.py checks of the emulated sort.  --emulated-sort: both arrays come from that sort instead (sa_emu.h: the
+// bodies of device/sa_kernel.h over the whole batch), so that sort -> search -> walk -> BWT emit runs as one chain.
 #include "wave_emu.h"
 
 #include <string>
 #include <vector>
 
 #include "lz77_kernel.h"
+#include "sa_emu.h"
 #include "zpaq_amd.h"
 
 namespace {
@@ -47,7 +50,9 @@ void bwt_thunk(void* p) { Args* a = (Args*)p; zpq::bwt_emit_body(a->in_all, a->s
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 8) { fprintf(stderr, "usage: lz77_emu <kind> <min_match> <lookahead> <bucket> <checkbits> <out_prefix> <input>...\n"); return 2; }
+  const bool emulated_sort = argc > 1 && !strcmp(argv[1], "--emulated-sort");
+  if (emulated_sort) { --argc; ++argv; }
+  if (argc < 8) { fprintf(stderr, "usage: lz77_emu [--emulated-sort] <kind> <min_match> <lookahead> <bucket> <checkbits> <out_prefix> <input>...\n"); return 2; }
   const uint32_t kind = (uint32_t)atoi(argv[1]), min_match = (uint32_t)atoi(argv[2]), lookahead = (uint32_t)atoi(argv[3]),
                  bucket = (uint32_t)atoi(argv[4]), checkbits = (uint32_t)atoi(argv[5]);
   const std::string prefix = argv[6];
@@ -57,8 +62,10 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> sa_all, rank_all;
   std::vector<uint16_t> blk;
   uint64_t ntok = 0;
+  std::vector<std::vector<uint8_t>> ins(nb);
+  for (unsigned b = 0; b < nb; ++b) ins[b] = slurp(argv[7 + b]);
   for (unsigned b = 0; b < nb; ++b) {
-    const std::vector<uint8_t> in = slurp(argv[7 + b]);
+    const std::vector<uint8_t>& in = ins[b];
     zpq::LzBlock& B = blocks[b];
     memset(&B, 0, sizeof B);
     B.off = in_all.size();
@@ -68,15 +75,22 @@ int main(int argc, char** argv) {
     B.tok_off = ntok;
     B.tok_cap = kind == 3 ? 0u : B.n / (min_match ? min_match : 1u) + 2u;
     ntok += B.tok_cap;
+    in_all.insert(in_all.end(), in.begin(), in.end());
+    blk.insert(blk.end(), B.n, (uint16_t)b);
+    if (emulated_sort) continue;
     std::vector<uint32_t> sa(in.size() + 1), rank(in.size() + 1);
     if (zpq_suffix_array_host(in.data(), B.n, sa.data()) != 0) { fprintf(stderr, "suffix array: %s\n", zpq_last_error()); return 2; }
     for (uint32_t j = 0; j < B.n; ++j) rank[sa[j]] = j + 1;
-    in_all.insert(in_all.end(), in.begin(), in.end());
     sa_all.insert(sa_all.end(), sa.begin(), sa.begin() + B.n);
     rank_all.insert(rank_all.end(), rank.begin(), rank.begin() + B.n);
-    blk.insert(blk.end(), B.n, (uint16_t)b);
   }
   const uint64_t total = in_all.size();
+  if (emulated_sort && total) {
+    const sa_emu::Batch S = sa_emu::build(ins);
+    sa_all.assign(S.sa, S.sa + total);
+    rank_all.assign(S.rank, S.rank + total);
+    blk.assign(S.blk, S.blk + total);          // (the search and the BWT emit take the sorter's element -> block map too)
+  }
   in_all.resize(total + 64);                 // (the engine's input buffer is padded as well; nothing may read it)
   std::vector<uint4> res(total + 1);
   std::vector<zpq::LzTok> toks(ntok + 1);

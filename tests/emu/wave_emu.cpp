@@ -30,6 +30,10 @@ struct Fiber {
 };
 
 static const size_t kStack = 512 * 1024;
+// stacks of finished fibers, kept for the next launch: a kernel of a few statements per lane (the suffix sort's) otherwise spends
+// its time in mmap / munmap and in the first touch of a fresh stack
+static std::vector<void*> g_stack_pool;
+static const size_t kStackPoolMax = 4096;
 static std::vector<Fiber> g_fibers;
 static Fiber* g_cur = nullptr;
 static void* g_sched_sp = nullptr;
@@ -133,8 +137,13 @@ void run_grid(KernelFn fn, void* args, unsigned threads, unsigned nblocks, unsig
     Fiber& f = g_fibers[i];
     f.tid = i % threads;
     f.wg = i / threads;
-    f.stack = mmap(nullptr, kStack, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    if (f.stack == MAP_FAILED) { perror("mmap"); abort(); }
+    if (!g_stack_pool.empty()) {
+      f.stack = g_stack_pool.back();
+      g_stack_pool.pop_back();
+    } else {
+      f.stack = mmap(nullptr, kStack, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+      if (f.stack == MAP_FAILED) { perror("mmap"); abort(); }
+    }
     uintptr_t top = ((uintptr_t)f.stack + kStack) & ~(uintptr_t)15;
     void** sp = (void**)top;
     *--sp = nullptr;                 // keeps the entry frame 16-byte aligned like a real call
@@ -215,7 +224,10 @@ void run_grid(KernelFn fn, void* args, unsigned threads, unsigned nblocks, unsig
     if (!ran) { fprintf(stderr, "wave_emu: deadlock -- the lanes of a wavefront disagree about the next cross-lane operation "
                            "(one sits in divergent control flow) or a barrier is not reached by every thread\n"); abort(); }
   }
-  for (Fiber& f : g_fibers) munmap(f.stack, kStack);
+  for (Fiber& f : g_fibers) {
+    if (g_stack_pool.size() < kStackPoolMax) g_stack_pool.push_back(f.stack);
+    else munmap(f.stack, kStack);
+  }
   g_fibers.clear();
   g_lds.clear();
 }

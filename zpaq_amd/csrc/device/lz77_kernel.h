@@ -14,8 +14,10 @@
 //                        the chain i -> i + length and lists the matches taken
 //   bwt_emit_kernel      one lane per suffix: the byte in front of it (255 for the whole string; its index on the side)
 //
-// The inverse suffix array is the rank array the sorter ends with (device/sa_kernels.hip).  Bit-exact by construction; the
-// emulator runs this file against the host's parse (tests/emu/lz77_emu_main.cpp), the GPU tests against the reference's archives.
+// The inverse suffix array is the rank array the sorter ends with (device/sa_kernels.hip; device/sa_kernel.h on the emulator:
+// tests/test_emu_sa.py holds it to the host sorter's inverse + 1).  Bit-exact by construction; the emulator runs this file
+// against the host's parse (tests/emu/lz77_emu_main.cpp, with the host sorter's arrays and once with the emulated sort's), the
+// GPU tests against the reference's archives.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>

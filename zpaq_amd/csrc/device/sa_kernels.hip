@@ -9,6 +9,7 @@
 //   keep a rank, a flag + prefix sum gives the others theirs, relative to the block's first element.  After the round
 //   ranks order the suffixes by their first 2h bytes; when every key of a round is distinct the ranks are the inverse
 //   suffix array.  log2(longest repeat) rounds: 3-4 for random data, 6-8 for text, log2(n) for a block of zeros.
+//   The kernels' bodies and the loop's two decisions are in device/sa_kernel.h (the emulator runs them: tests/emu/sa_emu_main.cpp).
 //
 // Each round streams the arrays a few times at HBM rate (radix sort of 64-bit keys + 32-bit values, one gather, one
 // scan, one scatter): bandwidth work, no MFMA.  Blocks of up to 2^24 bytes and 65 535 blocks per call; the caller
@@ -25,58 +26,28 @@
 #include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
+#include "sa_kernel.h"
 #include "sa_kernels.h"
 
 namespace zpq {
 
 namespace {
 
-// rank of round 0: byte + 1 (1..256); block id and position of every element
 __global__ __launch_bounds__(256) void sa_init_kernel(const uint8_t* const* in, const uint64_t* off, uint32_t nblocks, uint64_t total,
                                                       uint32_t* rank, uint16_t* blk) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  // block of element i: binary search in off[0..nblocks]
-  uint32_t lo = 0, hi = nblocks;
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-  blk[i] = (uint16_t)lo;
-  rank[i] = (uint32_t)in[lo][i - off[lo]] + 1u;
+  sa_init_body(in, off, nblocks, total, rank, blk);
 }
-
 __global__ __launch_bounds__(256) void sa_keys_kernel(const uint32_t* rank, const uint16_t* blk, const uint64_t* off, uint64_t total, uint32_t h,
                                                       uint64_t* keys, uint32_t* vals) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const uint32_t b = blk[i];
-  const uint64_t end = off[b + 1];
-  const uint32_t r2 = i + h < end ? rank[i + h] : 0u;
-  keys[i] = (uint64_t)b << 48 | (uint64_t)rank[i] << 24 | r2;
-  vals[i] = (uint32_t)i;
+  sa_keys_body(rank, blk, off, total, h, keys, vals);
 }
-
-// 1 where a sorted key differs from its left neighbour (the first element of the array counts as different)
-__global__ __launch_bounds__(256) void sa_flags_kernel(const uint64_t* keys, uint64_t total, uint32_t* flags) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= total) return;
-  flags[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1u : 0u;
-}
-
-// new rank of the element at sorted position j: names counted from the block's first sorted position (= off[block]: the
-// block id is the major key), starting at 1
+__global__ __launch_bounds__(256) void sa_flags_kernel(const uint64_t* keys, uint64_t total, uint32_t* flags) { sa_flags_body(keys, total, flags); }
 __global__ __launch_bounds__(256) void sa_rename_kernel(const uint64_t* keys, const uint32_t* vals, const uint32_t* scan, const uint64_t* off,
                                                         uint64_t total, uint32_t* rank) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= total) return;
-  const uint32_t b = (uint32_t)(keys[j] >> 48);
-  rank[vals[j]] = scan[j] - scan[off[b]] + 1u;
+  sa_rename_body(keys, vals, scan, off, total, rank);
 }
-
-// ranks are a permutation of 1..n_b inside every block now: sa[off_b + rank - 1] = position in the block
 __global__ __launch_bounds__(256) void sa_invert_kernel(const uint32_t* rank, const uint16_t* blk, const uint64_t* off, uint64_t total, uint32_t* sa) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const uint64_t o = off[blk[i]];
-  sa[o + rank[i] - 1u] = (uint32_t)(i - o);
+  sa_invert_body(rank, blk, off, total, sa);
 }
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -179,14 +150,12 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
   const size_t tmp_bytes = ws_bytes - (size_t)(p - (uint8_t*)ws);
   const unsigned g = grid_for(total);
   hipLaunchKernelGGL(sa_init_kernel, dim3(g), dim3(256), 0, st, d_in, d_off, nblocks, total, rank, blk);
-  // bits of the key that matter: block id on top of two 24-bit ranks
-  unsigned blk_bits = 1;
-  while ((1u << blk_bits) < nblocks) ++blk_bits;
+  const unsigned key_bits = sa_key_bits(nblocks);
   uint32_t h = 1, rounds = 0;
   for (;; h <<= 1) {
     hipLaunchKernelGGL(sa_keys_kernel, dim3(g), dim3(256), 0, st, rank, blk, d_off, total, h, keys, vals);
     size_t need = tmp_bytes;
-    hipError_t e = rocprim::radix_sort_pairs(tmp, need, keys, keys2, vals, vals2, (size_t)total, 0, 48 + blk_bits, st);
+    hipError_t e = rocprim::radix_sort_pairs(tmp, need, keys, keys2, vals, vals2, (size_t)total, 0, key_bits, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sa_flags_kernel, dim3(g), dim3(256), 0, st, keys2, total, flags);
     need = tmp_bytes;
@@ -194,13 +163,12 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sa_rename_kernel, dim3(g), dim3(256), 0, st, keys2, vals2, flags, d_off, total, rank);
     ++rounds;
-    // every key distinct <=> the last prefix sum equals the number of elements
-    uint32_t names = 0;
+    uint32_t names = 0;                                              // the last prefix sum
     e = hipMemcpyAsync(&names, flags + (total - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(st);
     if (e != hipSuccess) return e;
-    if ((uint64_t)names == total || h >= max_len) break;
+    if (sa_round_is_last(names, total, h, max_len)) break;
   }
   hipLaunchKernelGGL(sa_invert_kernel, dim3(g), dim3(256), 0, st, rank, blk, d_off, total, d_sa);
   if (rounds_out) *rounds_out = rounds;
