@@ -374,6 +374,27 @@ int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, con
  * routes, and no measurement exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.
  * The bytes are the same either way. */
 uint32_t zpq_last_device_unbwt_segments(void);
+/* The same for a batch of streams of an E8E9 method: args[1] = 4 (the filter alone: the stream is the filtered block), 5 / 6 (in
+ * front of LZ77 level 1 / 2) or 7 (in front of the BWT, at args[0] <= 4 only).  The stream goes through the stage's decoder as
+ * in zpq_lz77_decode_device / zpq_bwt_decode_device, with the method's own parameters, and the inverse filter runs over the
+ * result while it is on the device (device/e8e9_kernel.h: the scan is serial only along chains of candidates, a lane walks each
+ * from its first e8 / e9).  status[b]: 0 decoded -- out[b] holds, byte for byte, what zpq_postprocess_block makes of stream b,
+ * outlen[b] its size; 1 declined -- out[b] is untouched, outlen[b] is 0 and the caller runs the program on the host: whatever
+ * the stage in front declines (an output beyond 2^(args[0] + 20) bytes among it: the programs filter M, which wraps there), or
+ * a chain that one lane did not finish in 2^20 serial steps.  The device never gives a verdict on a damaged stream.  When a
+ * decoded block does not fit its buffer every size is reported and nothing is written (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED with
+ * a note in zpq_last_error without a device, for another kind of method, or outside the range (65 535 streams and 2 GiB of
+ * output per batch; the stage's workspace, the outputs and 4 bytes per e8 / e9 candidate and chain within the device budget). */
+int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                           uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that went that way.  A segment qualifies when its block has one segment
+ * and carries, byte for byte, one of the E8E9 programs compressBlock's methods generate: the filter alone (x.,4..), in front of
+ * LZ77 (x.,5.., x.,6..) or in front of the BWT at args[0] <= 4 (x.,7..); custom programs, the BWT at args[0] > 4 and blocks of
+ * several segments never do.  ZPAQ_AMD_DEVICE_UNE8=0|1 forces the route off or on for qualifying segments; unset it is off: it
+ * is taken only from a measured group size of 64 segments or more at which it beat both other routes, and no measurement
+ * exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  ZPAQ_AMD_DEVICE_UNLZ and
+ * ZPAQ_AMD_DEVICE_UNBWT never touch these segments.  The bytes are the same either way. */
+uint32_t zpq_last_device_une8_segments(void);
 void zpq_e8e9(uint8_t* data, uint32_t n);      /* e8e9 (libzpaq.cpp:6450-6459), in place */
 /* Compiler alone (libzpaq.cpp:2698): ZPAQL source text -> header / PCOMP bytes. */
 int zpq_assemble(const char* config, const int* args9, uint8_t* hcomp, size_t hcap,

@@ -670,6 +670,35 @@ int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, con
 
 uint32_t zpq_last_device_unbwt_segments(void) { return last_device_unbwt_segments(); }
 
+// ... and for a batch of streams of an E8E9 method (device/e8e9_kernel.h behind the stage's decoder)
+int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                           size_t* outlen, int32_t* status) {
+  ZPQ_TRY
+  if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  (void)make_config(xmethod, args);
+  if (xmethod[0] == '0' || args[1] < 4 || args[1] > 7 || (args[1] == 7 && args[0] > 4))
+    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not an E8E9 method (args[1] 4 .. 7, the BWT at args[0] <= 4)");
+  std::vector<Une8Job> jobs;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
+    outlen[i] = 0;
+    status[i] = 1;
+    jobs.push_back(Une8Job{stream[i], len[i], out[i], cap[i], nullptr});
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
+  std::string note;
+  const int got = engine_e8e9_decode(args[1], lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
+  for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
+  if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }
+
 int zpq_sha1_batch_device(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out20n) {
   ZPQ_TRY
   if (n && (!in || !len || !out20n)) fail(ZPQ_E_ARG, "null argument");

@@ -1998,12 +1998,56 @@ int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<
   return 1;
 }
 
+// device/e8e9_kernel.h over blocks that lie in io_out, in place.  The caller placed them (offsets multiples of 16, the rooms rounded
+// up) and ensured une8_ws(..).bytes of io_out at ws_off (a multiple of 256) for the first half: the block table, the tiles' counts,
+// the statuses, the scan's scratch.  The list of seeds and breaks is sized from the two totals the host reads between the halves
+// and goes to io_in, whose content the caller needs no longer; `held` = what the batch holds besides it.  status[k] = 0: block k
+// is filtered; 1: a lane gave it up, its bytes are to be dropped.  false + note: nothing is to be delivered.
+struct E8Ws { uint64_t o_cnt, o_st, o_tmp, bytes; size_t tmp_bytes; };
+static E8Ws une8_ws(size_t m, uint64_t ntiles) {
+  E8Ws w;
+  w.o_cnt = (m * sizeof(E8Block) + 255) & ~255ull;
+  w.o_st = (w.o_cnt + 4 * (2 * ntiles + 1) + 255) & ~255ull;
+  w.o_tmp = (w.o_st + 4 * m + 255) & ~255ull;
+  w.tmp_bytes = une8_scan_bytes((uint32_t)ntiles);
+  w.bytes = w.o_tmp + w.tmp_bytes + 256;
+  return w;
+}
+static bool une8_run(Engine& e, uint64_t ws_off, const std::vector<E8Block>& blk, uint64_t ntiles, uint64_t held, std::vector<uint32_t>& status,
+                     std::string& note) {
+  const size_t m = blk.size();
+  status.assign(m, 1u);
+  if (!m) return true;
+  const E8Ws w = une8_ws(m, ntiles);
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  uint8_t* const wb = ob + ws_off;
+  uint32_t* const cnt = (uint32_t*)(wb + w.o_cnt);
+  HIP_CHECK(hipMemcpyAsync(wb, blk.data(), m * sizeof(E8Block), hipMemcpyHostToDevice, e.stream));
+  hipError_t rc = launch_une8_mark(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)(wb + w.o_st), wb + w.o_tmp, w.tmp_bytes, e.stream);
+  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device E8E9 filter failed: ") + hipGetErrorString(rc); return false; }
+  uint32_t nseeds = 0, nlist = 0;
+  HIP_CHECK(hipMemcpyAsync(&nseeds, cnt + ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipMemcpyAsync(&nlist, cnt + 2 * ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (nseeds) {
+    if (held + 4ull * nlist + (1u << 20) > e.budget) { note = "the filter's list exceeds the device budget"; return false; }
+    e.io_in.ensure(4ull * nlist + 64);
+    rc = launch_une8_walk(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)e.io_in.p, nseeds, kE8MaxSteps, (uint32_t*)(wb + w.o_st), e.stream);
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device E8E9 filter failed: ") + hipGetErrorString(rc); return false; }
+  }
+  HIP_CHECK(hipMemcpyAsync(status.data(), wb + w.o_st, 4 * m, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  return true;
+}
+
 // device/lz77_decode_kernel.h for a batch of host streams: one upload, the parse, 12 bytes per stream back, the outputs placed
-// back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.
-int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note) {
+// back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.  e8: the method's program filters
+// M before it writes it out -- the outputs are placed for device/e8e9_kernel.h, which runs over them before they go down.
+template <class Job>
+static int lz77_decode_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<Job>& jobs, std::string& note, bool e8) {
   const size_t n = jobs.size();
   if (!n) return 1;
-  for (UnlzJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  for (Job& j : jobs) { j.status = 1; j.out_len = 0; }
   if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
   std::vector<UnlzStream> st(n);
   uint64_t in_bytes = 0, ntok = 0;
@@ -2049,25 +2093,38 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
   HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, n * sizeof(UnlzResult), hipMemcpyDeviceToHost, e.stream));
   HIP_CHECK(hipStreamSynchronize(e.stream));
   std::vector<uint64_t> off(n);
-  uint64_t room = 0;
+  uint64_t room = 0, tiles = 0;
   bool fits = true, any = false;
+  std::vector<E8Block> fb;                          // e8: the decoded blocks as the filter sees them, fb[k] is jobs[fwho[k]]
+  std::vector<size_t> fwho;
   for (size_t i = 0; i < n; ++i) {
     off[i] = room;
     if (res[i].status != kUnlzOk) continue;
     jobs[i].out_len = res[i].out_len;
-    room += res[i].out_len;
+    if (e8) {
+      fb.push_back(E8Block{room, res[i].out_len, (uint32_t)tiles});
+      fwho.push_back(i);
+      tiles += e8_tiles(res[i].out_len);
+    }
+    room += e8 ? e8_room(res[i].out_len) : res[i].out_len;
     any = true;
     if (!jobs[i].vec && res[i].out_len > jobs[i].cap) fits = false;
   }
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
-  if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Job& j : jobs) j.out_len = 0; return -1; }
+  const uint64_t f_off = e8 ? (room + 255) & ~255ull : room, f_ws = e8 ? une8_ws(fb.size(), tiles).bytes : 0;
+  if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; for (Job& j : jobs) j.out_len = 0; return -1; }
   if (!fits) return 0;
+  std::vector<uint32_t> fst;
   if (any) {
-    e.io_out.ensure(room + 64);
+    e.io_out.ensure(f_off + f_ws + 64);
     HIP_CHECK(hipMemcpyAsync(ab + o_off, off.data(), 8 * n, hipMemcpyHostToDevice, e.stream));
     rc = launch_unlz_copy((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (const UnlzResult*)(ab + o_res),
                           (const uint64_t*)(ab + o_off), (uint8_t*)e.io_out.p, e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); for (UnlzJob& j : jobs) j.out_len = 0; return -1; }
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); for (Job& j : jobs) j.out_len = 0; return -1; }
+    if (e8) {
+      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { for (Job& j : jobs) j.out_len = 0; return -1; }
+      for (size_t k = 0; k < fb.size(); ++k) if (fst[k] != 0) { res[fwho[k]].status = kUnlzLong; jobs[fwho[k]].out_len = 0; }
+    }
     for (size_t i = 0; i < n; ++i) {
       if (res[i].status != kUnlzOk) continue;
       if (jobs[i].vec) jobs[i].vec->resize(res[i].out_len);
@@ -2079,14 +2136,18 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
   for (size_t i = 0; i < n; ++i) if (res[i].status == kUnlzOk) jobs[i].status = 0;
   return 1;
 }
+int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note) {
+  return lz77_decode_batch(level, rb, min_match, mbits, jobs, note, false);
+}
 
 // device/bwt_decode_kernel.h for a batch of host streams.  The host admits the streams (the rule, the range), so every size is
 // known and the room is checked before anything runs; then one upload, the six kernels, a word per stream back, and the outputs
-// of the streams whose path was whole down.
-int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note) {
+// of the streams whose path was whole down.  e8: as for lz77_decode_batch.
+template <class Job>
+static int bwt_decode_batch(U32 mbits, std::vector<Job>& jobs, std::string& note, bool e8) {
   const size_t n = jobs.size();
   if (!n) return 1;
-  for (UnbwtJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  for (Job& j : jobs) { j.status = 1; j.out_len = 0; }
   if (n > 65535 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
   std::vector<BwtStream> st;
   std::vector<size_t> who;                          // st[k] is jobs[who[k]]
@@ -2094,7 +2155,7 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
   uint64_t in_bytes = 0, nodes = 0, tiles = 0, splits = 0, room = 0;
   bool fits = true;
   for (size_t i = 0; i < n; ++i) {
-    const UnbwtJob& j = jobs[i];
+    const Job& j = jobs[i];
     if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
     BwtStream S;
     memset(&S, 0, sizeof(S));
@@ -2108,14 +2169,14 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
     nodes += (uint64_t)S.n + 1;
     tiles += bwt_tiles(S.n);
     splits += bwt_splitters(S.n);
-    room += S.n;
+    room += e8 ? e8_room(S.n) : S.n;
     jobs[i].out_len = S.n;
     if (!j.vec && S.n > j.cap) fits = false;
     st.push_back(S);
     who.push_back(i);
   }
   const size_t m = st.size();
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Job& j : jobs) j.out_len = 0; return -1; }
   if (!fits) return 0;
   if (m) {
     Engine& e = eng();
@@ -2129,14 +2190,17 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
     const uint64_t o_st = (o_sp + 16 * splits + 255) & ~255ull;
     const uint64_t o_res = (o_st + m * sizeof(BwtStream) + 255) & ~255ull;
     const uint64_t ws = o_res + 4 * m + 256;
-    if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+    uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
+    for (size_t k = 0; k < m && e8; ++k) f_tiles += e8_tiles(st[k].n);
+    const uint64_t f_off = e8 ? (room + 255) & ~255ull : room, f_ws = e8 ? une8_ws(m, f_tiles).bytes : 0;
+    if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; for (Job& j : jobs) j.out_len = 0; return -1; }
     e.io_in.ensure(in_bytes + 64);
-    e.io_out.ensure(room + 64);
+    e.io_out.ensure(f_off + f_ws + 64);
     e.arena.ensure(ws);
     uint8_t* const ab = (uint8_t*)e.arena.p;
     std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
     for (size_t k = 0; k < m; ++k) {
-      const UnbwtJob& j = jobs[who[k]];
+      const Job& j = jobs[who[k]];
       uint8_t* at = stage.get() + st[k].in_off;
       memcpy(at, j.in, j.in_len);
       memset(at + j.in_len, 0, (size_t)((0u - j.in_len) & 3u));
@@ -2145,12 +2209,26 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
     HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
     const hipError_t rc = launch_bwt_decode((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (uint32_t)m, (uint32_t)tiles, (uint32_t)splits,
                                             (uint32_t*)(ab + o_hist), (uint32_t*)ab, ab + o_sp, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device BWT decoder failed: ") + hipGetErrorString(rc); for (UnbwtJob& j : jobs) j.out_len = 0; return -1; }
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device BWT decoder failed: ") + hipGetErrorString(rc); for (Job& j : jobs) j.out_len = 0; return -1; }
     std::vector<uint32_t> res(m);
     HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
     HIP_CHECK(hipStreamSynchronize(e.stream));
+    if (e8) {
+      std::vector<E8Block> fb;
+      std::vector<size_t> fk;
+      std::vector<uint32_t> fst;
+      uint64_t tiles = 0;
+      for (size_t k = 0; k < m; ++k) {
+        if (res[k] != 0) continue;
+        fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
+        fk.push_back(k);
+        tiles += e8_tiles(st[k].n);
+      }
+      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { for (Job& j : jobs) j.out_len = 0; return -1; }
+      for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
+    }
     for (size_t k = 0; k < m; ++k) {
-      UnbwtJob& j = jobs[who[k]];
+      Job& j = jobs[who[k]];
       if (res[k] != 0) { j.out_len = 0; continue; }
       if (j.vec) j.vec->resize(st[k].n);
       uint8_t* dst = j.vec ? j.vec->data() : j.out;
@@ -2160,6 +2238,60 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
     for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
   }
   for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
+  return 1;
+}
+int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note) { return bwt_decode_batch(mbits, jobs, note, false); }
+
+// Streams of the E8E9 methods back into their blocks: the stage in front with the method's own parameters (kind 5 / 6: the LZ77
+// decoder, kind 7: the BWT decoder, kind 4: none -- the stream is the filtered block), then device/e8e9_kernel.h over its output
+// while that is still on the device.
+int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<Une8Job>& jobs, std::string& note) {
+  if (kind == 5 || kind == 6) return lz77_decode_batch((U32)(kind - 4), rb, min_match, mbits, jobs, note, true);
+  if (kind == 7) return bwt_decode_batch(mbits, jobs, note, true);
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (Une8Job& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || kind != 4) { note = "batch outside the device filter's range"; return -1; }
+  std::vector<E8Block> fb(n);
+  uint64_t room = 0, tiles = 0;
+  bool fits = true;
+  for (size_t i = 0; i < n; ++i) {
+    fb[i] = E8Block{room, jobs[i].in_len, (uint32_t)tiles};
+    room += e8_room(jobs[i].in_len);
+    tiles += e8_tiles(jobs[i].in_len);
+    jobs[i].out_len = jobs[i].in_len;
+    if (!jobs[i].vec && jobs[i].in_len > jobs[i].cap) fits = false;
+  }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Une8Job& j : jobs) j.out_len = 0; return -1; }
+  if (!fits) return 0;
+  Engine& e = eng();
+  std::lock_guard<std::mutex> g(e.mu);
+  require_ready(e);
+  bind_device(e);
+  wait_in_flight(e);
+  const uint64_t f_off = (room + 255) & ~255ull, f_ws = une8_ws(n, tiles).bytes;
+  if (f_off + f_ws + (1u << 20) > e.budget) { note = "the blocks exceed the device budget"; for (Une8Job& j : jobs) j.out_len = 0; return -1; }
+  e.io_out.ensure(f_off + f_ws + 64);
+  if (room) {
+    std::unique_ptr<uint8_t[]> stage(new uint8_t[room]);
+    for (size_t i = 0; i < n; ++i) {
+      uint8_t* at = stage.get() + fb[i].off;
+      if (jobs[i].in_len) memcpy(at, jobs[i].in, jobs[i].in_len);
+      memset(at + jobs[i].in_len, 0, (size_t)(e8_room(jobs[i].in_len) - jobs[i].in_len));
+    }
+    HIP_CHECK(hipMemcpyAsync(e.io_out.p, stage.get(), room, hipMemcpyHostToDevice, e.stream));
+  }
+  std::vector<uint32_t> fst;
+  if (!une8_run(e, f_off, fb, tiles, f_off + f_ws, fst, note)) { for (Une8Job& j : jobs) j.out_len = 0; return -1; }
+  for (size_t i = 0; i < n; ++i) {
+    Une8Job& j = jobs[i];
+    if (fst[i] != 0) { j.out_len = 0; continue; }
+    if (j.vec) j.vec->resize(j.in_len);
+    uint8_t* dst = j.vec ? j.vec->data() : j.out;
+    if (j.in_len) HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + fb[i].off, j.in_len, hipMemcpyDeviceToHost, e.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t i = 0; i < n; ++i) if (fst[i] == 0) jobs[i].status = 0;
   return 1;
 }
 

@@ -142,6 +142,20 @@ int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note)
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
 inline bool bwt_unbwt_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
+// Streams of the E8E9 methods back into their blocks on the device: kind = args[1], 5 / 6 the LZ77 decoder of level 1 / 2 (rb,
+// min_match, mbits as for engine_lz77_decode), 7 the BWT decoder (mbits as for engine_bwt_decode), 4 nothing -- then the inverse
+// filter over the stage's output while it is on the device (device/e8e9_kernel.h: candidates, seeds and breaks marked from the
+// original bytes, a lane per chain's first seed walks it), then the blocks down.  What the method's program makes of each stream,
+// or status 1: declined, the output untouched -- whatever the stage in front declines (an output beyond 2^mbits among it: the
+// programs filter M, which wraps there), and a block in which a lane gave up after kE8MaxSteps serial steps.  1 / 0 / -1 as for
+// engine_lz77_decode (kinds 4 and 7 know every size before anything runs); 65 535 streams and 2 GiB of output per batch; the
+// tiles' counts and the list of seeds and breaks (4 bytes each) count against the engine's budget.
+struct Une8Job { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
+int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<Une8Job>& jobs, std::string& note);
+// Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNE8 is unset.  The rule is the one of
+// lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
+// all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
+inline bool e8_une8_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)
 

@@ -269,6 +269,17 @@ static inline bool bwt_stream_empty(const uint8_t* s, uint64_t len) {      // wh
   return len == 5 && s[0] == 255u && !s[1] && !s[2] && !s[3] && !s[4];
 }
 
+// The inverse E8E9 filter over blocks that lie in one device buffer, in place (device/e8e9_kernel.h)
+enum { kE8Lane = 16, kE8Tile = 4096 };                 // bytes per lane of the mark pass, per workgroup of 256 lanes
+static const uint32_t kE8MaxSteps = 1u << 20;          // serial steps after which a lane gives its block up (a safety: declined)
+struct E8Block {
+  uint64_t off;          // first byte in the buffer, a multiple of kE8Lane; the room behind the block is rounded up to kE8Lane
+  uint32_t n;            // bytes
+  uint32_t tile_off;     // first tile: e8_tiles(n) of them
+};
+static inline uint32_t e8_tiles(uint32_t n) { return n ? (uint32_t)(((uint64_t)n + kE8Tile - 1u) / kE8Tile) : 1u; }
+static inline uint64_t e8_room(uint64_t n) { return (n + kE8Lane - 1u) & ~(uint64_t)(kE8Lane - 1u); }
+
 // Cap on HCOMP instructions per input byte: the reference has no limit (a
 // hostile header can loop forever); a device kernel must not hang.
 static const uint32_t kMaxVmSteps = 1u << 20;

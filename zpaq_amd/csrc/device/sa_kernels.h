@@ -59,4 +59,15 @@ hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, ui
 // not n nodes and nothing of it was written.
 hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t ntiles, uint32_t nsplit, uint32_t* hist,
                              uint32_t* link, void* splitters, uint32_t* status, uint8_t* out_all, hipStream_t st);
+// The inverse E8E9 filter over blocks in one device buffer, in place (device/e8e9_kernel.h).  blocks[b] = {off, n, tile_off}: off a
+// multiple of 16 with the room behind the block rounded up to 16, ntiles = the sum of e8_tiles(n).  launch_une8_mark leaves in
+// cnt (2 * ntiles + 1 words) the exclusive prefix sums of the tiles' seed and break counts and zeroes status[0 .. nblocks); tmp:
+// une8_scan_bytes(ntiles) bytes.  The caller reads cnt[ntiles] (the seeds) and cnt[2 * ntiles] (seeds + breaks = the words of
+// `list`) and calls launch_une8_walk, which rewrites the blocks; status[b] = 1: a lane gave block b up after max_steps steps, its
+// bytes are neither the input nor the output.
+size_t une8_scan_bytes(uint32_t ntiles);
+hipError_t launch_une8_mark(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt, uint32_t* status, void* tmp,
+                            size_t tmp_bytes, hipStream_t st);
+hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
+                            uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st);
 }  // namespace zpq

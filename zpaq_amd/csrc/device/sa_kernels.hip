@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "bwt_decode_kernel.h"
+#include "e8e9_kernel.h"
 #include "lz77_codes_kernel.h"
 #include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
@@ -115,6 +116,19 @@ __global__ __launch_bounds__(64) void unbwt_offsets_kernel(const BwtStream* stre
 __global__ __launch_bounds__(256) void unbwt_emit_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link, const uint4* sp,
                                                          const uint32_t* status, uint8_t* out_all) {
   unbwt_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
+}
+
+__global__ __launch_bounds__(256) void une8_mark_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt,
+                                                        uint32_t* status) {
+  une8_mark_body(buf, blocks, nblocks, ntiles, cnt, status);
+}
+__global__ __launch_bounds__(256) void une8_scatter_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles,
+                                                           const uint32_t* scan, uint32_t* list) {
+  une8_scatter_body(buf, blocks, nblocks, ntiles, scan, list);
+}
+__global__ __launch_bounds__(256) void une8_walk_kernel(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan,
+                                                        const uint32_t* list, uint32_t nseeds, uint32_t max_steps, uint32_t* status) {
+  une8_walk_body(buf, blocks, nblocks, ntiles, scan, list, nseeds, max_steps, status);
 }
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -293,6 +307,35 @@ hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, ui
   hipLaunchKernelGGL(unbwt_offsets_kernel, dim3(nstreams), dim3(64), 0, st, streams, sp, status);
   hipLaunchKernelGGL(unbwt_emit_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint32_t*)link, (const uint4*)sp,
                      (const uint32_t*)status, out_all);
+  return hipGetLastError();
+}
+
+size_t une8_scan_bytes(uint32_t ntiles) {
+  size_t scan_tmp = 0;
+  (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)2 * ntiles + 1, rocprim::plus<uint32_t>());
+  return up256(scan_tmp) + 256;
+}
+
+// device/e8e9_kernel.h, the first half: the counts per tile, scanned in place, and the blocks' statuses zeroed
+hipError_t launch_une8_mark(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt, uint32_t* status, void* tmp,
+                            size_t tmp_bytes, hipStream_t st) {
+  if (!nblocks) return hipSuccess;
+  if (nblocks > 65535u || ntiles < nblocks || ntiles >= (1u << 30) || tmp_bytes < une8_scan_bytes(ntiles)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(une8_mark_kernel, dim3(ntiles), dim3(256), 0, st, buf, blocks, nblocks, ntiles, cnt, status);
+  size_t need = tmp_bytes;
+  const hipError_t e = rocprim::exclusive_scan(tmp, need, cnt, cnt, 0u, (size_t)2 * ntiles + 1, rocprim::plus<uint32_t>(), st);
+  if (e != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// ... the second half: the list (nlist = scan[2 * ntiles] words, the first nseeds = scan[ntiles] of them seeds), then the walk
+hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
+                            uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st) {
+  if (!nblocks || !nseeds) return hipSuccess;                   // (no seed: no hit, the breaks alone are not needed)
+  if (nblocks > 65535u || ntiles < nblocks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(une8_scatter_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t*)buf, blocks, nblocks, ntiles, scan, list);
+  hipLaunchKernelGGL(une8_walk_kernel, dim3(grid_for(nseeds)), dim3(256), 0, st, buf, blocks, nblocks, ntiles, scan, (const uint32_t*)list, nseeds,
+                     max_steps, status);
   return hipGetLastError();
 }
 

@@ -524,7 +524,7 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
 }
 
 namespace {
-std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0};
+std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0};
 
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
@@ -579,14 +579,51 @@ int device_unbwt_mode() {
   if (!v || !*v) return 2;
   return v[0] == '0' ? 0 : 1;
 }
+// The programs of the E8E9 methods -- the filter alone (",4": ph = pm = 0, the same program whatever args[0]), in front of LZ77
+// level 1 (",5") and level 2 (",6,mm"), in front of the BWT at args[0] <= 4 (",7") -- recognised the same way.
+struct Une8Program { int kind; U32 rb, min_match, mbits; };
+bool une8_program(const std::vector<U8>& key, Une8Program& u) {
+  if (key.size() < 3) return false;
+  std::vector<U8> k1, k2;
+  if (key[0] == 0 && key[1] == 0) {
+    if (!unlz_generated(0, ",4", k1) || k1 != key) return false;
+    u = Une8Program{4, 0u, 0u, 0u};
+    return true;
+  }
+  const int a0 = (int)key[1] - 20;
+  if (a0 < 0 || a0 > 11) return false;
+  if (key[0] == key[1]) {
+    if (a0 > 4 || !unlz_generated(a0, ",7", k1) || k1 != key) return false;
+    u = Une8Program{7, 0u, 0u, (U32)key[1]};
+    return true;
+  }
+  if (key[0] != 0) return false;
+  if (unlz_generated(a0, ",5", k1) && k1 == key) { u = Une8Program{5, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
+  if (!unlz_generated(a0, ",6,1", k1) || !unlz_generated(a0, ",6,2", k2) || k1.size() != key.size() || k2.size() != key.size()) return false;
+  size_t at = key.size(), differ = 0;
+  for (size_t i = 0; i < key.size(); ++i) if (k1[i] != k2[i]) { at = i; ++differ; }
+  if (differ != 1) return false;
+  const U32 mm = key[at];
+  if (!unlz_generated(a0, ",6," + std::to_string(mm), k1) || k1 != key) return false;
+  u = Une8Program{6, 0u, mm, (U32)key[1]};
+  return true;
+}
+// ZPAQ_AMD_DEVICE_UNE8: 0 never, 1 always, unset (2): when e8_une8_pays says so (device/engine.hpp)
+int device_une8_mode() {
+  const char* v = getenv("ZPAQ_AMD_DEVICE_UNE8");
+  if (!v || !*v) return 2;
+  return v[0] == '0' ? 0 : 1;
+}
 }  // namespace
 
 U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_order_relaxed); }
 U32 last_device_unbwt_segments() { return g_last_unbwt_segments.load(std::memory_order_relaxed); }
+U32 last_device_une8_segments() { return g_last_une8_segments.load(std::memory_order_relaxed); }
 
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
   g_last_unlz_segments.store(0, std::memory_order_relaxed);
   g_last_unbwt_segments.store(0, std::memory_order_relaxed);
+  g_last_une8_segments.store(0, std::memory_order_relaxed);
   struct Seg {
     FoundSegment fs;
     zpq_plan* plan = nullptr;     // null: stored block
@@ -770,6 +807,37 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
         kv.second.swap(left);
       }
       g_last_unbwt_segments.store(taken, std::memory_order_relaxed);
+    }
+    // The E8E9 methods likewise: their stage's decoder, then the inverse filter over its output on the device
+    // (device/e8e9_kernel.h: the scan is serial only along short chains).  ZPAQ_AMD_DEVICE_UNE8=0|1 forces it off or on, unset
+    // follows e8_une8_pays.
+    const int une8 = mode ? 0 : device_une8_mode();
+    if (une8 && nprog && engine_device_count() > 0) {
+      U32 taken = 0;
+      for (auto& kv : by_prog) {
+        const std::vector<U8>& key = kv.first;
+        Une8Program u;
+        if (kv.second.empty() || !une8_program(key, u)) continue;
+        const size_t skip = 3 + (key.size() - 2);
+        U64 bytes = 0;
+        std::vector<Une8Job> uj;
+        for (size_t i : kv.second) {
+          const Seg& s = *segs[i];
+          uj.push_back(Une8Job{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
+          bytes += s.decoded.size() - skip;
+        }
+        if (une8 != 1 && !e8_une8_pays(uj.size(), bytes)) continue;
+        std::string note;
+        if (engine_e8e9_decode(u.kind, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
+        std::vector<size_t> left;
+        for (size_t k = 0; k < uj.size(); ++k) {
+          const size_t i = kv.second[k];
+          if (uj[k].status == 0) { on_device[i] = 1; ++taken; }
+          else { done[i].clear(); left.push_back(i); }
+        }
+        kv.second.swap(left);
+      }
+      g_last_une8_segments.store(taken, std::memory_order_relaxed);
     }
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
       for (auto& kv : by_prog) {

@@ -63,6 +63,8 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
 U32 last_device_unlz_segments();
 // ... that device/bwt_decode_kernel.h decoded
 U32 last_device_unbwt_segments();
+// ... that went through their stage's decoder and device/e8e9_kernel.h (the E8E9 methods)
+U32 last_device_une8_segments();
 
 // PostProcessor (libzpaq.cpp:2183-2241) of one block: the first segment's decoded bytes start with the PP header
 // (0 = PASS, or 1 len16 PCOMP program); every later segment of the block continues in the same mode -- PASS copies,
