@@ -395,6 +395,36 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
  * exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  ZPAQ_AMD_DEVICE_UNLZ and
  * ZPAQ_AMD_DEVICE_UNBWT never touch these segments.  The bytes are the same either way. */
 uint32_t zpq_last_device_une8_segments(void);
+/* The archiver's fragmenting (zpaq.cpp `add`): every file is cut into content-defined fragments, each is hashed with SHA-1 and
+ * the archiver deduplicates on the hash before it packs blocks.  zpq_fragment_limits: the smallest and largest fragment for
+ * -fragment `fragment` (a negative one counts as 0) and the method's block size (2^(20 + N) - 4096; below 13 counts as 13).
+ * zpq_fragment_host: the serial scan over n files.  nfrag[f] = the fragments of file f; then, for all fragments in order,
+ * size[k], hits[k] (predictions of the fragment's order-1 table that held), sha1[20 k ..] and o1[256 k ..] (the table at the cut).
+ * An empty file is one empty fragment; a file whose last byte is a cut ends with one more, empty, fragment; the SHA-1 of an
+ * empty fragment is the SHA-1 of nothing.  *total = the fragments of the batch; when cap is smaller nothing else is written and
+ * the call returns ZPQ_E_OVERFLOW.
+ * zpq_fragment_device: the same results from the device (device/fragment_kernel.h): a wavefront walks each piece
+ * of a file 64 positions at a time, the host stitches the pieces' lists where their cuts meet, SHA-1 runs per fragment on the
+ * device.  ZPQ_E_UNSUPPORTED with a note in zpq_last_error without a device or outside the range: 65 535 files and 2 GiB per
+ * batch, the files and their record lists (2 * 264 bytes per smallest fragment) within the device budget.  ZPAQ_AMD_FRAG_PIECE
+ * (bytes, read per call) overrides the piece size of 256 KiB, or 64 smallest fragments where that is more (tests).  zpq_last_fragment_rounds: the fix-up rounds of this process's
+ * last zpq_fragment_device call (0: every piece began at a cut; data that never re-joins, such as constant bytes, takes one
+ * round per piece).
+ * zpq_fragment_analyze: what the archiver computes for a fragment that did not deduplicate (zpaq.cpp:2436-2471) from its o1,
+ * size and hits and the tables of the last four such fragments of the block, o1prev[4 * 256], oldest first, zero at the start of a
+ * block: returns the final hits (the redundancy estimate), *text1 and *exe1 = 0 | 1.  The caller advances o1prev as the archiver
+ * does (2530-2533): only behind a fragment of at least the smallest size, the four tables move down by one (the oldest leaves) and
+ * the fragment's o1 becomes the last.  It runs on the host: which fragments deduplicate is the archiver's knowledge. */
+void zpq_fragment_limits(int fragment, uint32_t blocksize, uint32_t* min_frag, uint32_t* max_frag);
+int zpq_fragment_host(const uint8_t* const* in, const uint64_t* len, uint32_t n, int fragment, uint32_t blocksize,
+                      uint32_t* nfrag /* [n] */, uint32_t* size, uint32_t* hits, uint8_t* sha1 /* 20 each */,
+                      uint8_t* o1 /* 256 each */, size_t cap, size_t* total);
+int zpq_fragment_device(const uint8_t* const* in, const uint64_t* len, uint32_t n, int fragment, uint32_t blocksize,
+                        uint32_t* nfrag /* [n] */, uint32_t* size, uint32_t* hits, uint8_t* sha1 /* 20 each */,
+                        uint8_t* o1 /* 256 each */, size_t cap, size_t* total);
+uint32_t zpq_last_fragment_rounds(void);
+uint32_t zpq_fragment_analyze(const uint8_t* o1 /* 256 */, uint64_t sz, uint32_t hits, const uint8_t* o1prev /* 1024 */,
+                              int* text1, int* exe1);
 void zpq_e8e9(uint8_t* data, uint32_t n);      /* e8e9 (libzpaq.cpp:6450-6459), in place */
 /* Compiler alone (libzpaq.cpp:2698): ZPAQL source text -> header / PCOMP bytes. */
 int zpq_assemble(const char* config, const int* args9, uint8_t* hcomp, size_t hcap,

@@ -97,6 +97,16 @@ def lib():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_last_device_une8_segments.restype = C.c_uint32
     L.zpq_last_device_une8_segments.argtypes = []
+    _frag = [C.POINTER(_u8p), C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+             C.POINTER(C.c_uint32), _u8p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.zpq_fragment_host.argtypes = _frag
+    L.zpq_fragment_device.argtypes = _frag
+    L.zpq_fragment_limits.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.zpq_fragment_limits.restype = None
+    L.zpq_last_fragment_rounds.restype = C.c_uint32
+    L.zpq_last_fragment_rounds.argtypes = []
+    L.zpq_fragment_analyze.restype = C.c_uint32
+    L.zpq_fragment_analyze.argtypes = [_u8p, C.c_uint64, C.c_uint32, _u8p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -387,6 +397,78 @@ def e8e9_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], gua
 def last_device_une8_segments() -> int:
     """Segments of the last decompress call that went through the device's inverse E8E9 filter (ZPAQ_AMD_DEVICE_UNE8)."""
     return int(lib().zpq_last_device_une8_segments())
+
+
+def fragment_limits(fragment: int, blocksize: int) -> Tuple[int, int]:
+    """zpq_fragment_limits: (smallest, largest) fragment of -fragment `fragment` at the method's block size."""
+    lo, hi = C.c_uint32(0), C.c_uint32(0)
+    lib().zpq_fragment_limits(int(fragment), int(blocksize), C.byref(lo), C.byref(hi))
+    return int(lo.value), int(hi.value)
+
+
+def _fragment(entry, files: Sequence, fragment: int, blocksize: int, cap: Optional[int]):
+    n = len(files)
+    ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in files]
+    IA = (_u8p * max(n, 1))(*[_p(a) for a in ins])
+    IL = (C.c_uint64 * max(n, 1))(*[len(x) for x in files])
+    NF = (C.c_uint32 * max(n, 1))()
+    total = C.c_size_t(0)
+    if cap is None:                                 # ask for the count first: nothing is written when cap is too small
+        rc = entry(IA, IL, n, int(fragment), int(blocksize), NF, None, None, None, None, 0, C.byref(total))
+        if rc not in (0, 3):
+            return rc, None, int(total.value)
+        cap = int(total.value)
+    fill = 0xEE
+    size = np.full(cap + 1, 0xEEEEEEEE, np.uint32)
+    hits = np.full(cap + 1, 0xEEEEEEEE, np.uint32)
+    sha = np.full(20 * (cap + 1), fill, np.uint8)
+    o1 = np.full(256 * (cap + 1), fill, np.uint8)
+    u32p = C.POINTER(C.c_uint32)
+    for k in range(n):
+        NF[k] = 0xEEEEEEEE
+    rc = entry(IA, IL, n, int(fragment), int(blocksize), NF, size.ctypes.data_as(u32p), hits.ctypes.data_as(u32p), _p(sha), _p(o1), cap,
+               C.byref(total))
+    t = int(total.value)
+    if rc != 0:
+        untouched = (all(NF[k] == 0xEEEEEEEE for k in range(n)) and bool((size == 0xEEEEEEEE).all()) and bool((hits == 0xEEEEEEEE).all())
+                     and bool((sha == fill).all()) and bool((o1 == fill).all()))
+        return rc, untouched, t
+    assert size[cap] == 0xEEEEEEEE and hits[cap] == 0xEEEEEEEE and (sha[20 * cap:] == fill).all() and (o1[256 * cap:] == fill).all()
+    out, k = [], 0
+    for f in range(n):
+        fr = []
+        for _ in range(int(NF[f])):
+            fr.append((int(size[k]), int(hits[k]), sha[20 * k:20 * k + 20].tobytes(), o1[256 * k:256 * k + 256].tobytes()))
+            k += 1
+        out.append(fr)
+    assert k == t
+    return 0, out, t
+
+
+def fragment_host(files: Sequence, fragment: int, blocksize: int, cap: Optional[int] = None):
+    """zpq_fragment_host: the archiver's content-defined fragments of a batch of files, by the serial scan.  Returns (return code,
+    per file a list of (size, hits, sha1, o1), the batch's fragment count).  cap None: the count is asked for first.  When the call
+    fails the second element says whether the output arrays were left untouched."""
+    return _fragment(lib().zpq_fragment_host, files, fragment, blocksize, cap)
+
+
+def fragment_device(files: Sequence, fragment: int, blocksize: int, cap: Optional[int] = None):
+    """zpq_fragment_device: the same from the device (device/fragment_kernel.h)."""
+    return _fragment(lib().zpq_fragment_device, files, fragment, blocksize, cap)
+
+
+def last_fragment_rounds() -> int:
+    """Fix-up rounds of the last fragment_device call."""
+    return int(lib().zpq_last_fragment_rounds())
+
+
+def fragment_analyze(o1: bytes, sz: int, hits: int, o1prev: bytes) -> Tuple[int, int, int]:
+    """zpq_fragment_analyze: (final hits, text1, exe1) of a fragment against the four tables in front of it."""
+    a, b = _arr(o1), _arr(o1prev)
+    assert a.size == 256 and b.size == 1024
+    t, x = C.c_int(0), C.c_int(0)
+    h = lib().zpq_fragment_analyze(_p(a), int(sz), int(hits), _p(b), C.byref(t), C.byref(x))
+    return int(h), int(t.value), int(x.value)
 
 
 def compress_block(data, method: str, filename: Optional[str] = None, comment: Optional[str] = None,

@@ -699,6 +699,74 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }
 
+// The archiver's fragmenting (host/fragment.cpp; on the device: device/fragment_kernel.h through engine_fragment)
+void zpq_fragment_limits(int fragment, uint32_t blocksize, uint32_t* min_frag, uint32_t* max_frag) {
+  if (blocksize < 13u) blocksize = 13u;
+  const FragLimits l = fragment_limits(fragment, blocksize);
+  if (min_frag) *min_frag = l.min_frag;
+  if (max_frag) *max_frag = l.max_frag;
+}
+
+namespace {
+int fragment_deliver(const std::vector<std::vector<Fragment>>& fr, uint32_t n, uint32_t* nfrag, uint32_t* size, uint32_t* hits, uint8_t* sha1,
+                     uint8_t* o1, size_t cap, size_t* total) {
+  size_t all = 0;
+  for (uint32_t f = 0; f < n; ++f) all += fr[f].size();
+  *total = all;
+  if (all > cap) fail(ZPQ_E_OVERFLOW, "output arrays too small");
+  if (all && (!size || !hits || !sha1 || !o1)) fail(ZPQ_E_ARG, "null argument");
+  size_t k = 0;
+  for (uint32_t f = 0; f < n; ++f) {
+    nfrag[f] = (uint32_t)fr[f].size();
+    for (const Fragment& x : fr[f]) {
+      size[k] = x.size;
+      hits[k] = x.hits;
+      memcpy(sha1 + 20 * k, x.sha1, 20);
+      memcpy(o1 + 256 * k, x.o1, 256);
+      ++k;
+    }
+  }
+  return ZPQ_OK;
+}
+void fragment_args(const uint8_t* const* in, const uint64_t* len, uint32_t n, uint32_t blocksize, const uint32_t* nfrag, const size_t* total) {
+  if (!total || (n && (!in || !len || !nfrag))) fail(ZPQ_E_ARG, "null argument");
+  if (blocksize < 13u) fail(ZPQ_E_ARG, "blocksize below 13");
+  for (uint32_t f = 0; f < n; ++f) if (!in[f] && len[f]) fail(ZPQ_E_ARG, "null argument");
+}
+}  // namespace
+
+int zpq_fragment_host(const uint8_t* const* in, const uint64_t* len, uint32_t n, int fragment, uint32_t blocksize, uint32_t* nfrag, uint32_t* size,
+                      uint32_t* hits, uint8_t* sha1, uint8_t* o1, size_t cap, size_t* total) {
+  ZPQ_TRY
+  fragment_args(in, len, n, blocksize, nfrag, total);
+  const FragLimits lim = fragment_limits(fragment, blocksize);
+  std::vector<std::vector<Fragment>> fr(n);
+  for (uint32_t f = 0; f < n; ++f) fragment_scan(in[f], len[f], lim, true, fr[f]);
+  return fragment_deliver(fr, n, nfrag, size, hits, sha1, o1, cap, total);
+  ZPQ_CATCH
+}
+
+int zpq_fragment_device(const uint8_t* const* in, const uint64_t* len, uint32_t n, int fragment, uint32_t blocksize, uint32_t* nfrag, uint32_t* size,
+                        uint32_t* hits, uint8_t* sha1, uint8_t* o1, size_t cap, size_t* total) {
+  ZPQ_TRY
+  fragment_args(in, len, n, blocksize, nfrag, total);
+  *total = 0;
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "fragmenting on the device unavailable: no device");
+  const FragLimits lim = fragment_limits(fragment, blocksize);
+  std::vector<std::vector<Fragment>> fr;
+  std::string note;
+  if (engine_fragment(in, len, n, lim, fr, note) != 1) fail(ZPQ_E_UNSUPPORTED, "fragmenting on the device unavailable: " + note);
+  return fragment_deliver(fr, n, nfrag, size, hits, sha1, o1, cap, total);
+  ZPQ_CATCH
+}
+
+uint32_t zpq_last_fragment_rounds(void) { return engine_last_fragment_rounds(); }
+
+uint32_t zpq_fragment_analyze(const uint8_t* o1, uint64_t sz, uint32_t hits, const uint8_t* o1prev, int* text1, int* exe1) {
+  if (!o1 || !o1prev) return hits;
+  return fragment_analyze(o1, sz, hits, o1prev, text1, exe1);
+}
+
 int zpq_sha1_batch_device(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out20n) {
   ZPQ_TRY
   if (n && (!in || !len || !out20n)) fail(ZPQ_E_ARG, "null argument");

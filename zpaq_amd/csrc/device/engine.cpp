@@ -22,6 +22,7 @@
 
 #include "../host/codegen.hpp"
 #include "kernels.h"
+#include "fragment_stitch.hpp"
 #include "launch_policy.hpp"
 #include "sa_kernels.h"
 #include "spec_loader.hpp"
@@ -2292,6 +2293,127 @@ int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<U
   }
   HIP_CHECK(hipStreamSynchronize(e.stream));
   for (size_t i = 0; i < n; ++i) if (fst[i] == 0) jobs[i].status = 0;
+  return 1;
+}
+
+// device/fragment_kernel.h for a batch of host files: one upload, round 0 (every piece from its own start), the stitch rounds
+// (engine.hpp), one SHA-1 job per final fragment.  The records of a launch come back in runs of neighbouring lists.
+namespace {
+std::atomic<U32> g_last_fragment_rounds{0};
+}
+U32 engine_last_fragment_rounds() { return g_last_fragment_rounds.load(std::memory_order_relaxed); }
+
+int engine_fragment(const U8* const* in, const U64* len, U32 n, const FragLimits& lim, std::vector<std::vector<Fragment>>& out, std::string& note) {
+  out.assign(n, std::vector<Fragment>());
+  g_last_fragment_rounds.store(0, std::memory_order_relaxed);
+  if (!n) return 1;
+  U64 piece = std::max<U64>(kFragPiece, 64ull * lim.min_frag);    // (walks re-join after a few fragments: keep that a fraction of a piece)
+  if (const char* v = getenv("ZPAQ_AMD_FRAG_PIECE")) { const long long x = atoll(v); if (x > 0) piece = (U64)x; }
+  piece = std::min<U64>(std::max<U64>(piece, 64), 1u << 30);
+  if (n > 65535) { note = "more than 65 535 files in one batch"; return -1; }
+  if (!lim.min_frag || lim.max_frag < lim.min_frag) { note = "fragment limits out of range"; return -1; }
+  std::vector<U64> off(n);
+  U64 bytes = 0;
+  for (U32 f = 0; f < n; ++f) {
+    off[f] = bytes;
+    if (len[f] > (1ull << 31)) { note = "more than 2 GiB of input in one batch"; return -1; }
+    bytes += (len[f] + 63) & ~63ull;
+  }
+  if (bytes > (1ull << 31)) { note = "more than 2 GiB of input in one batch"; return -1; }
+  FragPlan pl;
+  if (!frag_plan(len, n, piece, lim.min_frag, pl)) { note = "the record lists exceed the device budget"; return -1; }
+  const size_t m = pl.pc.size();
+  const U64 nrec = pl.nrec;
+  const bool pieces = pl.pieces;                    // fix-ups write into a second set of lists
+  const U64 rec_bytes = nrec * sizeof(FragRec) * (pieces ? 2u : 1u);
+  Engine& e = eng();
+  std::lock_guard<std::mutex> g(e.mu);
+  require_ready(e);
+  bind_device(e);
+  wait_in_flight(e);
+  if (bytes + rec_bytes + m * (sizeof(FragJob) + sizeof(FragResult)) + (1u << 20) > e.budget) { note = "the files and the record lists exceed the device budget"; return -1; }
+  e.io_in.ensure(bytes + 64);
+  e.io_out.ensure(rec_bytes + 64);
+  e.jobs.ensure(m * sizeof(FragJob));
+  e.results.ensure(m * sizeof(FragResult));
+  uint8_t* const ib = (uint8_t*)e.io_in.p;
+  FragRec* const recs = (FragRec*)e.io_out.p;
+  // the upload: a large file goes as it lies, runs of small ones through one staging buffer
+  const U64 kDirect = 1u << 20;
+  U64 small = 0;
+  for (U32 f = 0; f < n; ++f) if (len[f] < kDirect) small += (len[f] + 63) & ~63ull;
+  std::unique_ptr<uint8_t[]> stage(new uint8_t[small + 64]);
+  U64 at = 0;
+  for (U32 f = 0; f < n;) {
+    if (len[f] >= kDirect) { HIP_CHECK(hipMemcpyAsync(ib + off[f], in[f], len[f], hipMemcpyHostToDevice, e.stream)); ++f; continue; }
+    const U32 f0 = f;
+    const U64 at0 = at;
+    for (; f < n && len[f] < kDirect; ++f) {
+      if (len[f]) memcpy(stage.get() + at, in[f], len[f]);
+      at += (len[f] + 63) & ~63ull;
+    }
+    if (at > at0) HIP_CHECK(hipMemcpyAsync(ib + off[f0], stage.get() + at0, at - at0, hipMemcpyHostToDevice, e.stream));
+  }
+  FragParams P;
+  P.min_frag = lim.min_frag; P.max_frag = lim.max_frag; P.thresh = lim.thresh;
+  // one launch: the jobs up, the walk, how each ended and its records down (the jobs' lists ascend in the record array)
+  auto run = [&](const std::vector<FragJob>& jb, std::vector<FragResult>& rs, std::vector<std::vector<FragRec>>& lists) -> bool {
+    const size_t q = jb.size();
+    rs.resize(q);
+    lists.assign(q, std::vector<FragRec>());
+    HIP_CHECK(hipMemcpyAsync(e.jobs.p, jb.data(), q * sizeof(FragJob), hipMemcpyHostToDevice, e.stream));
+    const hipError_t rc = launch_frag_walk(ib, (const FragJob*)e.jobs.p, (uint32_t)q, P, recs, (FragResult*)e.results.p, e.stream);
+    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device fragment walk failed: ") + hipGetErrorString(rc); return false; }
+    HIP_CHECK(hipMemcpyAsync(rs.data(), e.results.p, q * sizeof(FragResult), hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    if (!frag_results_ok(jb, rs)) { note = "device fragment walk: a record list overflowed"; return false; }
+    std::vector<FragRec> tmp;
+    for (size_t i = 0; i < q;) {
+      size_t j = i;
+      const U64 a = jb[i].rec_off;
+      U64 b = a + rs[i].count;
+      while (j + 1 < q && jb[j + 1].rec_off - b <= 256u && jb[j + 1].rec_off + rs[j + 1].count - a <= (1u << 16)) { ++j; b = (U64)jb[j].rec_off + rs[j].count; }
+      tmp.resize((size_t)(b - a));
+      HIP_CHECK(hipMemcpyAsync(tmp.data(), recs + a, (size_t)(b - a) * sizeof(FragRec), hipMemcpyDeviceToHost, e.stream));
+      HIP_CHECK(hipStreamSynchronize(e.stream));
+      for (size_t k = i; k <= j; ++k) lists[k].assign(tmp.begin() + (jb[k].rec_off - a), tmp.begin() + (jb[k].rec_off - a) + rs[k].count);
+      i = j + 1;
+    }
+    return true;
+  };
+  std::vector<std::vector<FragRec>> fin;
+  U32 rounds = 0;
+  if (!frag_stitch(pl, off.data(), len, n, piece, run, fin, rounds, note)) return -1;
+  // one SHA-1 job per fragment
+  U64 total = 0;
+  for (U32 f = 0; f < n; ++f) total += fin[f].size();
+  if (total >= (1ull << 31)) { note = "too many fragments"; return -1; }
+  std::vector<Sha1Job> sj((size_t)total);
+  size_t s = 0;
+  for (U32 f = 0; f < n; ++f) {
+    uint32_t from = 0;
+    out[f].resize(fin[f].size());
+    for (size_t k = 0; k < fin[f].size(); ++k) {
+      const FragRec& r = fin[f][k];
+      Fragment& o = out[f][k];
+      o.size = r.end - from;
+      o.hits = r.hits;
+      memcpy(o.o1, r.o1, 256);
+      sj[s] = Sha1Job{ib + off[f] + from, o.size, (uint32_t)s};
+      ++s;
+      from = r.end;
+    }
+  }
+  e.sha_jobs.ensure((size_t)total * sizeof(Sha1Job));
+  e.sha_out.ensure((size_t)total * 20);
+  std::vector<uint8_t> dig((size_t)total * 20);
+  HIP_CHECK(hipMemcpyAsync(e.sha_jobs.p, sj.data(), (size_t)total * sizeof(Sha1Job), hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(launch_sha1((const Sha1Job*)e.sha_jobs.p, (uint32_t)total, (uint8_t*)e.sha_out.p, e.stream));
+  HIP_CHECK(hipMemcpyAsync(dig.data(), e.sha_out.p, (size_t)total * 20, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  s = 0;
+  for (U32 f = 0; f < n; ++f) for (Fragment& o : out[f]) { memcpy(o.sha1, dig.data() + 20 * s, 20); ++s; }
+  g_last_fragment_rounds.store(rounds, std::memory_order_relaxed);
   return 1;
 }
 

@@ -156,6 +156,21 @@ int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<U
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
 inline bool e8_une8_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
+// The archiver's content-defined fragments of a batch of files on the device (device/fragment_kernel.h): the files
+// are uploaded and divided into pieces of kFragPiece bytes, or 64 smallest fragments where that is more (ZPAQ_AMD_FRAG_PIECE, in
+// bytes, read per call, overrides both: tests).
+// Round 0 walks every piece from its own start as if a cut lay there.  Then the host stitches: the true start of a piece is the
+// last cut of the accepted list of the piece in front; where that is not the piece's own start a fix-up walks from it until one
+// of its cuts is in the piece's list -- from there the list is the truth -- or until it has passed the piece's end.  The fix-ups
+// of all pieces run in one launch per round on provisional starts (the last cuts of the lists as they stand); the host accepts
+// pieces in order while their starts were the true ones, the rest run again.  The first open piece of a file always has its true
+// start, so every round finishes a piece: data that never re-joins (constant bytes) degenerates to a serial walk and stays
+// exact.  Then one SHA-1 job per fragment (launch_sha1).  out[f] = the fragments of file f, exactly fragment_scan's.
+// 1 done; -1 + note: outside the range (65 535 files and 2 GiB of input per batch; the files and twice the worst-case record
+// lists, 264 bytes per min_frag bytes, within the engine's budget) -- nothing was delivered.
+static const U32 kFragPiece = 1u << 18;        // 256 KiB: 36 against 47 ms with 1 MiB on one file of 256 MiB
+int engine_fragment(const U8* const* in, const U64* len, U32 n, const FragLimits& lim, std::vector<std::vector<Fragment>>& out, std::string& note);
+U32 engine_last_fragment_rounds();     // fix-up rounds of this process's last engine_fragment call (0: every piece began at a cut)
 int engine_selftest(int32_t out[8]);
 int engine_jit_threads();      // host threads spec_precompile() uses by default (the host cores the process may use, at most 16)
 

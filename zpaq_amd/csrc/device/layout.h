@@ -280,6 +280,36 @@ struct E8Block {
 static inline uint32_t e8_tiles(uint32_t n) { return n ? (uint32_t)(((uint64_t)n + kE8Tile - 1u) / kE8Tile) : 1u; }
 static inline uint64_t e8_room(uint64_t n) { return (n + kE8Lane - 1u) & ~(uint64_t)(kE8Lane - 1u); }
 
+// The archiver's content-defined fragments of a batch of files that lie in one device buffer (device/fragment_kernel.h)
+struct FragParams {
+  uint32_t min_frag, max_frag;   // a cut needs min_frag bytes, max_frag bytes force one (host/fragment.cpp fragment_limits)
+  uint32_t thresh;               // a cut where h < thresh: 2^(22 - fragment), 0 = never (fragment > 22)
+};
+struct FragRec {                 // one fragment as a walk leaves it
+  uint32_t end;                  // offset in the file of the first byte behind it
+  uint32_t hits;                 // predictions of the order-1 table that held
+  uint8_t o1[256];               // the table at the cut
+};
+struct FragJob {                 // a wavefront's walk
+  uint64_t off;                  // the file's first byte in the buffer
+  uint32_t n;                    // the file's bytes
+  uint32_t start;                // the walk begins here as if a cut lay in front: a fresh state
+  uint32_t stop;                 // it ends at the first cut at or beyond this offset (a cut at n goes on to the end of file)
+  uint32_t rec_off, rec_cap;     // its list in the record array: first record, room
+  uint32_t merge_off, merge_cnt; // a fix-up: the list (ascending ends) of the piece it walks into; it ends at a cut found there
+};
+enum { kFragStop = 0, kFragEof = 1, kFragMerged = 2, kFragFull = 3 };
+struct FragResult {
+  uint32_t count;                // records written
+  uint32_t status;               // kFragStop: ended at a cut >= stop; kFragEof: the last record is the fragment that ran into the
+                                 // end of file; kFragMerged: the last record's end is merge list[merge_at].end; kFragFull: no room
+  uint32_t merge_at;
+};
+// the records a walk from `start` that ends at the first cut >= stop (or at the end of file) can write: a cut needs min_frag bytes
+static inline uint64_t frag_rec_cap(uint64_t start, uint64_t stop, uint32_t min_frag) {
+  return (stop > start ? stop - start : 0u) / (min_frag ? min_frag : 1u) + 3u;
+}
+
 // Cap on HCOMP instructions per input byte: the reference has no limit (a
 // hostile header can loop forever); a device kernel must not hang.
 static const uint32_t kMaxVmSteps = 1u << 20;

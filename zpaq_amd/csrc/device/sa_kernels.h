@@ -70,4 +70,9 @@ hipError_t launch_une8_mark(const uint8_t* buf, const E8Block* blocks, uint32_t 
                             size_t tmp_bytes, hipStream_t st);
 hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
                             uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st);
+// The archiver's content-defined fragments (device/fragment_kernel.h): a wavefront per job walks its file in `buf` from job.start
+// with a fresh state and appends a record per fragment to recs[job.rec_off ..], until the first cut at or beyond job.stop, a cut
+// whose end is in recs[job.merge_off .. + merge_cnt) (ascending ends), or the end of file; res[job] says how it ended.  The
+// caller sizes every list with frag_rec_cap (layout.h); a walk that finds no room ends with kFragFull and writes nothing behind it.
+hipError_t launch_frag_walk(const uint8_t* buf, const FragJob* jobs, uint32_t njobs, FragParams P, FragRec* recs, FragResult* res, hipStream_t st);
 }  // namespace zpq

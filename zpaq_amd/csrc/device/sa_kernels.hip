@@ -23,6 +23,7 @@
 
 #include "bwt_decode_kernel.h"
 #include "e8e9_kernel.h"
+#include "fragment_kernel.h"
 #include "lz77_codes_kernel.h"
 #include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
@@ -129,6 +130,11 @@ __global__ __launch_bounds__(256) void une8_scatter_kernel(const uint8_t* buf, c
 __global__ __launch_bounds__(256) void une8_walk_kernel(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan,
                                                         const uint32_t* list, uint32_t nseeds, uint32_t max_steps, uint32_t* status) {
   une8_walk_body(buf, blocks, nblocks, ntiles, scan, list, nseeds, max_steps, status);
+}
+
+__global__ __launch_bounds__(64) void frag_walk_kernel(const uint8_t* buf, const FragJob* jobs, uint32_t njobs, FragParams P, FragRec* recs,
+                                                       FragResult* res) {
+  frag_walk_body(buf, jobs, njobs, P, recs, res);
 }
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -336,6 +342,14 @@ hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblock
   hipLaunchKernelGGL(une8_scatter_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t*)buf, blocks, nblocks, ntiles, scan, list);
   hipLaunchKernelGGL(une8_walk_kernel, dim3(grid_for(nseeds)), dim3(256), 0, st, buf, blocks, nblocks, ntiles, scan, (const uint32_t*)list, nseeds,
                      max_steps, status);
+  return hipGetLastError();
+}
+
+// device/fragment_kernel.h: a wavefront per job
+hipError_t launch_frag_walk(const uint8_t* buf, const FragJob* jobs, uint32_t njobs, FragParams P, FragRec* recs, FragResult* res, hipStream_t st) {
+  if (!njobs) return hipSuccess;
+  if (!P.min_frag || P.max_frag < P.min_frag) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(frag_walk_kernel, dim3(njobs), dim3(64), 0, st, buf, jobs, njobs, P, recs, res);
   return hipGetLastError();
 }
 

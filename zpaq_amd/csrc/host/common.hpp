@@ -103,4 +103,13 @@ struct LzToken { U32 i, off, len, blit; };
 void lz77_host_tokens(const U8* data, U32 n, const int args[9], const U32* sa, std::vector<LzToken>& toks);
 void lz77_serialize(const U8* data, U32 n, const int args[9], const LzToken* toks, size_t ntok, std::vector<U8>& out);
 
+// ---- fragment.cpp: the archiver's content-defined fragments (zpaq.cpp:2194-2201, 2385-2471) ----
+struct FragLimits { U32 min_frag, max_frag, thresh; };       // thresh: a cut where h < thresh, 0 = the hash never cuts (fragment > 22)
+FragLimits fragment_limits(int fragment, U32 blocksize);      // blocksize >= 13
+struct Fragment { U32 size, hits; U8 o1[256]; U8 sha1[20]; };
+// the serial scan of one file, its fragments appended to `out` (at least one: the last is the one that ran into the end of file)
+void fragment_scan(const U8* data, U64 n, const FragLimits& lim, bool with_sha1, std::vector<Fragment>& out);
+// the redundancy / text / x86 analysis of a fragment that did not deduplicate; returns the final hits
+U32 fragment_analyze(const U8 o1[256], U64 sz, U32 hits, const U8 o1prev[1024], int* text1, int* exe1);
+
 }  // namespace zpq
