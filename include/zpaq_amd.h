@@ -395,6 +395,29 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
  * exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  ZPAQ_AMD_DEVICE_UNLZ and
  * ZPAQ_AMD_DEVICE_UNBWT never touch these segments.  The bytes are the same either way. */
 uint32_t zpq_last_device_une8_segments(void);
+/* The generic route on its own: the PCOMP program `code` (the bytes without the two length bytes, ph and pm as in the block
+ * header) over n raw streams on the device, one lane per stream (device/pcomp_kernel.h: the program is translated to HIP and
+ * compiled at run time unless a code object for it is cached).  hint[b] = the expected size of output b or 0 (a segment's size
+ * comment; may be null: all 0): it only sizes the first attempt, an output beyond it costs a second launch.  The batch is one
+ * launch and shares its fate: status[b] is 0 for every stream -- out[b] holds, byte for byte, what zpq_pcomp_host makes of
+ * stream b, outlen[b] its size -- or 1 for every stream: declined, nothing was written, outlen[b] is 0, zpq_last_error names the
+ * reason and the caller runs the batch on the host.  Declined are: any stream on which the device program stopped with a status
+ * (`error`, a path that leaves the program, the budget of 2^30 backward jumps per call), a hint or an output beyond 2^32 - 16
+ * bytes, a batch beyond the device budget.  The device never gives a verdict on a program or a stream.  When an output does
+ * not fit its buffer every size is reported and nothing is written (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED with a note in
+ * zpq_last_error without a device, or when the program has no kernel (arrays beyond ph 28 / pm 30, a failed compile). */
+int zpq_pcomp_device(const uint8_t* code, size_t codelen, int ph, int pm, const uint8_t* const* stream, const uint32_t* len,
+                     uint32_t n, const uint64_t* hint, uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* The host's INTERPRETER with the same program over one stream, then the end-of-segment call: what zpq_decompress gives for a
+ * block of one segment that carries the program, with the same errors (ZPQ_E_VM: `error`, an undefined instruction, leaving the
+ * program, the step limit of zpq_set_pcomp_step_limit) -- also for a standard program, which zpq_decompress runs translated.
+ * *outlen is the size also when the buffer is too small (ZPQ_E_OVERFLOW, nothing written). */
+int zpq_pcomp_host(const uint8_t* code, size_t codelen, int ph, int pm, const uint8_t* in, uint32_t len, uint8_t* out, size_t cap,
+                   size_t* outlen);
+/* Segments of this process's last zpq_decompress call whose block's own PCOMP program ran on the device through that route: the
+ * segments of blocks of one segment that carry a program, when the call holds 4 of them or 256 KiB (or ZPAQ_AMD_PCOMP=device),
+ * less those another device decoder took and those of a group the device handed back. */
+uint32_t zpq_last_device_pcomp_segments(void);
 /* The archiver's fragmenting (zpaq.cpp `add`): every file is cut into content-defined fragments, each is hashed with SHA-1 and
  * the archiver deduplicates on the hash before it packs blocks.  zpq_fragment_limits: the smallest and largest fragment for
  * -fragment `fragment` (a negative one counts as 0) and the method's block size (2^(20 + N) - 4096; below 13 counts as 13).

@@ -3,9 +3,13 @@
 decompressing a stored block that carries the program), (2) this library's host interpreter (zpq_decompress of the same archive),
 (3) the TRANSLATOR that serves the device (zpq_pcomp_source: ZPAQL -> straight-line HIP C++), whose output is compiled
 for the host against host/pcomp_host.h -- the way the standard programs are built into the library -- and run on the
-same bytes.  All three must write the same output (or all must fail).  No GPU.
+same bytes, and (4) the device's own text for the program -- device/pcomp_kernel.h's pcomp_body around the same translation --
+on the wavefront emulator with the engine's capacities and guard pages (tests/emu/pcomp_emu.py).  All four must write the same
+output (or all must fail).  No GPU.
 
     python tests/fuzz_pcomp.py [programs] [seed]
+
+From the command line every second program comes from random_program_with_forms: do .. until beside do .. while, and forward lj.
 """
 from __future__ import annotations
 
@@ -65,7 +69,37 @@ def random_program(rng: random.Random) -> str:
     return " ".join(code)
 
 
-def run(programs: int, seed: int, verbose: bool = True) -> int:
+def random_program_with_forms(rng: random.Random, ph: int, pm: int) -> str:
+    """The structured forms random_program leaves out: `do .. until` (bounded like its `do .. while`: d counts down) and forward
+    `lj` -- out of an if, over whole pieces of the program, out of a loop -- to the start of a later piece or to the final halt.
+    if / ifnot / else / endif and their long forms come from fuzz_host.random_code as before."""
+    import fuzz_host
+    import pcomp_cases as pc
+    drop = ("error", "lj", "jt", "jf", "jmp", "halt", "a+= $", "a= $")
+    pieces = []
+    for _ in range(rng.randrange(2, 6)):
+        code = fuzz_host.random_code(rng, 0, False)
+        if rng.random() < 0.6:
+            body = [w for w in fuzz_host.random_code(rng, 1, False) if not w.startswith(("d", "*d=", "a<>d"))]
+            code += ["d= %d" % rng.randrange(1, 40), "do"] + body + ["d--", "a=d"] + rng.choice([["a> 0", "while"], ["a== 0", "until"]])
+        code = [w for w in code if not w.startswith(drop)]
+        for _ in range(rng.randrange(0, 3)):
+            code.insert(rng.randrange(len(code) + 1), "out")
+        pieces.append(code)
+    # forward jumps: from a word boundary inside piece i to the label in front of a later piece (or of the final halt)
+    for i in range(len(pieces)):
+        if rng.random() < 0.6:
+            at = rng.randrange(len(pieces[i]) + 1)
+            pieces[i][at:at] = [rng.choice(["if", "ifnot"]), "lj @p%d" % rng.randrange(i + 1, len(pieces) + 1), "endif"]
+    text = " ".join("@p%d: " % i + " ".join(c) for i, c in enumerate(pieces)) + " @p%d: halt" % len(pieces)
+    return pc._resolved(pc.Program("fuzz", ph, pm, text, False))
+
+
+def run(programs: int, seed: int, verbose: bool = True, forms: bool = False) -> int:
+    """forms: every second program from random_program_with_forms (the others, and all of them without it, from random_program:
+    the programs of a seed stay what they were)."""
+    sys.path.insert(0, os.path.join(HERE, "emu"))
+    import pcomp_emu
     import zpaq_amd as z
     from oracle.oracle_py import Ref
     from zpaq_amd import corpus
@@ -85,7 +119,11 @@ def run(programs: int, seed: int, verbose: bool = True) -> int:
     with tempfile.TemporaryDirectory() as td:
         while done < programs:
             ph, pm = rng.randrange(0, 6), rng.randrange(0, 10)
-            cfg = "comp 0 0 %d %d 0 hcomp halt pcomp prog ; %s halt end" % (ph, pm, random_program(rng))
+            try:
+                prog = random_program_with_forms(rng, ph, pm) if forms and done % 2 else random_program(rng) + " halt"
+            except z.ZpaqError:
+                continue
+            cfg = "comp 0 0 %d %d 0 hcomp halt pcomp prog ; %s end" % (ph, pm, prog)
             try:
                 header, pcomp = z.assemble(cfg)
             except z.ZpaqError:
@@ -139,6 +177,15 @@ def run(programs: int, seed: int, verbose: bool = True) -> int:
             if (want is None) != (status != 0) or (want is not None and got != want):
                 print("TRANSLATION DIFFERS status", status, len(got), None if want is None else len(want), "\n" + cfg, flush=True)
                 return 1
+            # the device's text on the emulator, as engine_pcomp would run the stream (no size hint)
+            try:
+                outs, st4, _ = pcomp_emu.run(code, ph, pm, [data])
+            except RuntimeError as e:
+                print("EMULATED KERNEL FAILS", str(e)[-1500:], "\n" + cfg, flush=True)
+                return 1
+            if (want is None) != (outs is None) or (want is not None and outs[0] != want):
+                print("EMULATED KERNEL DIFFERS status", st4, None if outs is None else len(outs[0]), None if want is None else len(want), "\n" + cfg, flush=True)
+                return 1
             done += 1
             if verbose and done % 20 == 0:
                 print("%d programs ok (%.0f s; reference JIT != reference interpreter on %d)" % (done, time.time() - t0, jit_differs), flush=True)
@@ -147,4 +194,4 @@ def run(programs: int, seed: int, verbose: bool = True) -> int:
 
 if __name__ == "__main__":
     pos = [a for a in sys.argv[1:] if not a.startswith("--")]
-    sys.exit(run(int(pos[0]) if pos else 40, int(pos[1]) if len(pos) > 1 else 1))
+    sys.exit(run(int(pos[0]) if pos else 40, int(pos[1]) if len(pos) > 1 else 1, forms=True))

@@ -569,6 +569,14 @@ def test_random_pcomp_programs_three_ways(zlib_, ref):
     assert fuzz_pcomp.run(25, 20260926, verbose=False) == 0
 
 
+def test_random_pcomp_programs_with_until_and_forward_lj(zlib_, ref):
+    """The same four ways (the fourth: the device's own text for the program, pcomp_body around the translation, on the wavefront
+    emulator) with every second program from fuzz_pcomp.random_program_with_forms: do .. until, forward lj out of ifs, over
+    pieces of the program and out of loops.  (200 programs of seed 7 were run when this was added.)"""
+    import fuzz_pcomp
+    assert fuzz_pcomp.run(16, 20261018, verbose=False, forms=True) == 0
+
+
 def test_two_blocks_per_wavefront_decoder_compiles_with_hiprtc(zlib_):
     """A chain nobody prebuilt (method 5 on records: periodic models that depend on the data, 29 components) through the
     run-time compiler the engine would use for it (no GPU needed)."""

@@ -97,6 +97,11 @@ def lib():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_last_device_une8_segments.restype = C.c_uint32
     L.zpq_last_device_une8_segments.argtypes = []
+    L.zpq_pcomp_device.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
+                                   C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    L.zpq_pcomp_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, _u8p, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.zpq_last_device_pcomp_segments.restype = C.c_uint32
+    L.zpq_last_device_pcomp_segments.argtypes = []
     _frag = [C.POINTER(_u8p), C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
              C.POINTER(C.c_uint32), _u8p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.zpq_fragment_host.argtypes = _frag
@@ -397,6 +402,51 @@ def e8e9_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], gua
 def last_device_une8_segments() -> int:
     """Segments of the last decompress call that went through the device's inverse E8E9 filter (ZPAQ_AMD_DEVICE_UNE8)."""
     return int(lib().zpq_last_device_une8_segments())
+
+
+def pcomp_device(code: bytes, ph: int, pm: int, streams: Sequence, caps: Sequence[int], hints: Optional[Sequence[int]] = None, guard: int = 0,
+                 fill: int = 0):
+    """zpq_pcomp_device: the PCOMP program `code` (without its two length bytes) over a batch of raw streams on the device, one lane
+    per stream.  caps = the output capacities; `guard` bytes of `fill` lie behind each; hints = the expected sizes (None: all 0).
+    Returns (return code, buffers -- cap + guard bytes each, as the call left them --, sizes, statuses: 0 decoded, 1 declined)."""
+    n = len(streams)
+    ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in streams]
+    caps = [int(c) for c in caps]
+    outs = [np.full(max(c + guard, 1), fill, np.uint8) for c in caps]
+    IA = (_u8p * n)(*[_p(a) for a in ins])
+    IL = (C.c_uint32 * n)(*[len(x) for x in streams])
+    HI = (C.c_uint64 * n)(*[int(h) for h in (hints if hints is not None else [0] * n)])
+    OA = (_u8p * n)(*[_p(a) for a in outs])
+    OC = (C.c_size_t * n)(*caps)
+    OL = (C.c_size_t * n)()
+    ST = (C.c_int32 * n)()
+    code = bytes(code)
+    rc = lib().zpq_pcomp_device(code, len(code), int(ph), int(pm), IA, IL, n, HI, OA, OC, OL, ST)
+    return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
+
+
+def pcomp_host(code: bytes, ph: int, pm: int, stream, cap: Optional[int] = None):
+    """zpq_pcomp_host: the host's interpreter with the PCOMP program `code` (without its two length bytes) over one stream.
+    Returns (return code, output, size); 5 (ZPQ_E_VM) when the program stops with an error."""
+    a = _arr(stream)
+    src = a if a.size else np.zeros(1, np.uint8)
+    code = bytes(code)
+    ol = C.c_size_t(0)
+    if cap is None:                                   # ask for the size first
+        probe = np.zeros(1, np.uint8)
+        rc = lib().zpq_pcomp_host(code, len(code), int(ph), int(pm), _p(src), a.size, _p(probe), 0, C.byref(ol))
+        if rc not in (0, 3):
+            return rc, b"", 0
+        cap = int(ol.value)
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    rc = lib().zpq_pcomp_host(code, len(code), int(ph), int(pm), _p(src), a.size, _p(out), int(cap), C.byref(ol))
+    size = int(ol.value)
+    return rc, (out[:size].tobytes() if rc == 0 else b""), size
+
+
+def last_device_pcomp_segments() -> int:
+    """Segments of the last decompress call whose block's own PCOMP program ran on the device (device/pcomp_kernel.h)."""
+    return int(lib().zpq_last_device_pcomp_segments())
 
 
 def fragment_limits(fragment: int, blocksize: int) -> Tuple[int, int]:

@@ -699,6 +699,56 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }
 
+// A raw PCOMP program over a batch of raw streams on the device (device/pcomp_kernel.h through engine_pcomp) ...
+int zpq_pcomp_device(const uint8_t* code, size_t codelen, int ph, int pm, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                     const uint64_t* hint, uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status) {
+  ZPQ_TRY
+  if (!code || !codelen || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
+  if (ph < 0 || pm < 0 || ph > 255 || pm > 255) fail(ZPQ_E_ARG, "ph / pm outside a header byte");
+  std::vector<std::vector<U8>> res(n);
+  std::vector<PcompSeg> segs;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
+    outlen[i] = 0;
+    status[i] = 1;
+    segs.push_back(PcompSeg{stream[i], len[i], hint ? hint[i] : 0, &res[i]});
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "post-processing on the device unavailable: no device");
+  std::string note;
+  bool handed_back = false;
+  if (!engine_pcomp(code, codelen, ph, pm, segs, note, &handed_back)) {
+    if (!handed_back) fail(ZPQ_E_UNSUPPORTED, "post-processing on the device unavailable: " + note);
+    set_last_error(note);                 // declined: the caller runs the batch on the host
+    return ZPQ_OK;
+  }
+  bool fits = true;
+  for (uint32_t i = 0; i < n; ++i) { outlen[i] = res[i].size(); fits = fits && res[i].size() <= cap[i]; }
+  if (!fits) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!res[i].empty()) memcpy(out[i], res[i].data(), res[i].size());
+    status[i] = 0;
+  }
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+// ... and over one stream through the host's interpreter (host/postproc.cpp)
+int zpq_pcomp_host(const uint8_t* code, size_t codelen, int ph, int pm, const uint8_t* in, uint32_t len, uint8_t* out, size_t cap, size_t* outlen) {
+  ZPQ_TRY
+  if (!code || (!in && len) || !outlen) fail(ZPQ_E_ARG, "null argument");
+  if (ph < 0 || pm < 0 || ph > 255 || pm > 255) fail(ZPQ_E_ARG, "ph / pm outside a header byte");
+  *outlen = 0;
+  std::vector<U8> data;
+  pcomp_interpret(code, codelen, ph, pm, in, len, data);
+  *outlen = data.size();
+  if (data.size() > cap) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  if (!data.empty()) memcpy(out, data.data(), data.size());
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+uint32_t zpq_last_device_pcomp_segments(void) { return last_device_pcomp_segments(); }
+
 // The archiver's fragmenting (host/fragment.cpp; on the device: device/fragment_kernel.h through engine_fragment)
 void zpq_fragment_limits(int fragment, uint32_t blocksize, uint32_t* min_frag, uint32_t* max_frag) {
   if (blocksize < 13u) blocksize = 13u;

@@ -1518,7 +1518,8 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
   if (!timed) mark_in_flight(e, st);
 }
 
-bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note) {
+bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note, bool* handed_back) {
+  if (handed_back) *handed_back = false;
   if (segs.empty()) return true;
   Engine& e = eng();
   std::lock_guard<std::mutex> g(e.mu);
@@ -1527,6 +1528,7 @@ bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<Pc
   wait_in_flight(e);
   PcompKernel* k = pcomp_kernel_for(code, codelen, ph, pm, note);
   if (!k) return false;
+  if (handed_back) *handed_back = true;          // (every false from here on)
   const size_t n = segs.size();
   const uint64_t mbytes = ((1ull << pm) + 255) & ~255ull, hbytes = ((4ull << ph) + 255) & ~255ull;
   std::vector<uint64_t> cap(n);

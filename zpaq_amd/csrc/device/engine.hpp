@@ -63,9 +63,11 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
 
 // Post-processing on the device: every segment's stream (decoded bytes after the PP header) through its block's PCOMP
 // program, one lane per segment.  Returns false (note says why) when the program cannot run there: the caller then
-// uses the host interpreter.  out[i] receives segment i's data; hint[i] = expected size or 0.
+// uses the host interpreter.  out[i] receives segment i's data; hint[i] = expected size or 0.  *handed_back (when given) tells
+// the two kinds of false apart: true when the kernel exists and the SEGMENTS go back to the host (a device status, an output
+// beyond the kernel's 32-bit range, the device budget), false when the program has no kernel here.
 struct PcompSeg { const U8* in; U32 in_len; U64 hint; std::vector<U8>* out; };
-bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note);
+bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note, bool* handed_back = nullptr);
 void engine_sha1_host(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out);
 // Suffix arrays of host buffers, all in one device call (device/sa_kernels.hip: prefix doubling over the whole batch).
 // false + note when the device declines (then the host sorts): a buffer of 2^24 bytes or more, too many buffers, memory.

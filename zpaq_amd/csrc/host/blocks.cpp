@@ -524,7 +524,7 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
 }
 
 namespace {
-std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0};
+std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0}, g_last_pcomp_segments{0};
 
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
@@ -619,11 +619,13 @@ int device_une8_mode() {
 U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_order_relaxed); }
 U32 last_device_unbwt_segments() { return g_last_unbwt_segments.load(std::memory_order_relaxed); }
 U32 last_device_une8_segments() { return g_last_une8_segments.load(std::memory_order_relaxed); }
+U32 last_device_pcomp_segments() { return g_last_pcomp_segments.load(std::memory_order_relaxed); }
 
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
   g_last_unlz_segments.store(0, std::memory_order_relaxed);
   g_last_unbwt_segments.store(0, std::memory_order_relaxed);
   g_last_une8_segments.store(0, std::memory_order_relaxed);
+  g_last_pcomp_segments.store(0, std::memory_order_relaxed);
   struct Seg {
     FoundSegment fs;
     zpq_plan* plan = nullptr;     // null: stored block
@@ -840,6 +842,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
       g_last_une8_segments.store(taken, std::memory_order_relaxed);
     }
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
+      U32 taken = 0;
       for (auto& kv : by_prog) {
         if (kv.second.empty()) continue;
         const std::vector<U8>& key = kv.first;
@@ -851,9 +854,10 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
         }
         std::string note;
         if (engine_pcomp(key.data() + 2, key.size() - 2, key[0], key[1], ps, note))
-          for (size_t i : kv.second) on_device[i] = 1;
+          for (size_t i : kv.second) { on_device[i] = 1; ++taken; }
         else if (force_dev) fail(ZPQ_E_UNSUPPORTED, "PCOMP on the device unavailable: " + note);
       }
+      g_last_pcomp_segments.store(taken, std::memory_order_relaxed);
     }
   }
   // Host post-processing and the checksum are per block (its segments in order: one PostProcessor per block, only the

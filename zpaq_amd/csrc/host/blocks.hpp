@@ -65,6 +65,8 @@ U32 last_device_unlz_segments();
 U32 last_device_unbwt_segments();
 // ... that went through their stage's decoder and device/e8e9_kernel.h (the E8E9 methods)
 U32 last_device_une8_segments();
+// ... that ran their block's own PCOMP program on the device (device/pcomp_kernel.h through engine_pcomp)
+U32 last_device_pcomp_segments();
 
 // PostProcessor (libzpaq.cpp:2183-2241) of one block: the first segment's decoded bytes start with the PP header
 // (0 = PASS, or 1 len16 PCOMP program); every later segment of the block continues in the same mode -- PASS copies,
@@ -85,6 +87,11 @@ class PostProcessor {
 
 // whether the host runs this PCOMP program (code without its 2 length bytes) as C++ translated at build time
 bool pcomp_is_translated(const U8* code, size_t len, int ph, int pm);
+
+// One stream (a segment's decoded bytes behind the PP header) through the INTERPRETER with the program `code` (without its 2
+// length bytes) on a fresh machine, then the EOS call: what a block of one segment carrying that program decodes to, with the
+// same step limits -- also for a standard program, which segment() would run translated.  Fails as segment() fails.
+void pcomp_interpret(const U8* code, size_t len, int ph, int pm, const U8* in, size_t n, std::vector<U8>& data);
 
 // The same for a block of ONE segment: turns a decoded segment (PP header + payload) into the
 // segment's data -- either passing it through or running the PCOMP program it carries.

@@ -265,6 +265,15 @@ bool pcomp_is_translated(const U8* code, size_t len, int ph, int pm) {
   return translated(std::vector<U8>(code, code + len), ph, pm) != nullptr;
 }
 
+void pcomp_interpret(const U8* code, size_t len, int ph, int pm, const U8* in, size_t n, std::vector<U8>& data) {
+  data.clear();
+  if (len < 1 || len > 65535) fail(ZPQ_E_CORRUPT, "Empty PCOMP");
+  PcompVm vm(code, len, ph, pm, data);
+  vm.set_standard(standard_program(std::vector<U8>(code, code + len), ph, pm) != nullptr);
+  for (size_t i = 0; i < n; ++i) vm.run(in[i]);
+  vm.run(0xFFFFFFFFu);
+}
+
 void post_process(const std::vector<U8>& header, const std::vector<U8>& decoded, std::vector<U8>& data) {
   data.clear();
   PostProcessor pp(header[4], header[5]);
