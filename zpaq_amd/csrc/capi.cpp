@@ -611,90 +611,71 @@ int zpq_postprocess_block(const char* xmethod, const uint8_t* stream, uint32_t l
   ZPQ_CATCH
 }
 
-// ... for a batch of LZ77 streams on the device (device/lz77_decode_kernel.h)
-int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
-                           size_t* outlen, int32_t* status) {
+// ... for a batch of streams on the device.  What the three entries below share: `wrong` is the entry's own method check (null:
+// the method is its route's; else why not), `decode` its engine call over the jobs (1 done, 0 a buffer too small, -1 + note).
+static int decode_streams_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                                 size_t* outlen, int32_t* status, const char* (*wrong)(const char* xmethod, const int* args),
+                                 int (*decode)(const int* args, std::vector<StreamJob>& jobs, std::string& note)) {
   ZPQ_TRY
   if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
   int args[9];
   (void)make_config(xmethod, args);
-  const int level = args[1] & 3;
-  if (xmethod[0] == '0' || args[1] < 1 || args[1] > 3 || level < 1 || level > 2)
-    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not an LZ77 method of level 1 or 2 without E8E9");
-  std::vector<UnlzJob> jobs;
+  if (const char* why = wrong(xmethod, args)) fail(ZPQ_E_UNSUPPORTED, std::string("decoding on the device unavailable: ") + why);
+  std::vector<StreamJob> jobs;
   for (uint32_t i = 0; i < n; ++i) {
     if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
     outlen[i] = 0;
     status[i] = 1;
-    jobs.push_back(UnlzJob{stream[i], len[i], out[i], cap[i], nullptr});
+    jobs.push_back(StreamJob{stream[i], len[i], out[i], cap[i], nullptr});
   }
   if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
   std::string note;
-  const int got = engine_lz77_decode((U32)level, lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+  const int got = decode(args, jobs, note);
   if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
   for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
   if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
   for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
   return ZPQ_OK;
   ZPQ_CATCH
+}
+
+// LZ77 streams (device/lz77_decode_kernel.h)
+int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                           size_t* outlen, int32_t* status) {
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        const int level = args[1] & 3;
+        return xm[0] == '0' || args[1] < 1 || args[1] > 3 || level < 1 || level > 2 ? "not an LZ77 method of level 1 or 2 without E8E9" : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) {
+        return engine_lz77_decode((U32)(args[1] & 3), lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+      });
 }
 
 uint32_t zpq_last_device_unlz_segments(void) { return last_device_unlz_segments(); }
 
-// ... and for a batch of BWT streams on the device (device/bwt_decode_kernel.h)
+// ... BWT streams (device/bwt_decode_kernel.h)
 int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                           size_t* outlen, int32_t* status) {
-  ZPQ_TRY
-  if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
-  int args[9];
-  (void)make_config(xmethod, args);
-  if (xmethod[0] == '0' || args[1] != 3 || args[0] > 4)
-    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not a BWT method (level 3) without E8E9 at args[0] <= 4");
-  std::vector<UnbwtJob> jobs;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
-    outlen[i] = 0;
-    status[i] = 1;
-    jobs.push_back(UnbwtJob{stream[i], len[i], out[i], cap[i], nullptr});
-  }
-  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
-  std::string note;
-  const int got = engine_bwt_decode((U32)(args[0] + 20), jobs, note);
-  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
-  for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
-  if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
-  for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
-  return ZPQ_OK;
-  ZPQ_CATCH
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        return xm[0] == '0' || args[1] != 3 || args[0] > 4 ? "not a BWT method (level 3) without E8E9 at args[0] <= 4" : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) { return engine_bwt_decode((U32)(args[0] + 20), jobs, note); });
 }
 
 uint32_t zpq_last_device_unbwt_segments(void) { return last_device_unbwt_segments(); }
 
-// ... and for a batch of streams of an E8E9 method (device/e8e9_kernel.h behind the stage's decoder)
+// ... and streams of an E8E9 method (device/e8e9_kernel.h behind the stage's decoder)
 int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                            size_t* outlen, int32_t* status) {
-  ZPQ_TRY
-  if (!xmethod || (n && (!stream || !len || !out || !cap || !outlen || !status))) fail(ZPQ_E_ARG, "null argument");
-  int args[9];
-  (void)make_config(xmethod, args);
-  if (xmethod[0] == '0' || args[1] < 4 || args[1] > 7 || (args[1] == 7 && args[0] > 4))
-    fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: not an E8E9 method (args[1] 4 .. 7, the BWT at args[0] <= 4)");
-  std::vector<Une8Job> jobs;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!stream[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
-    outlen[i] = 0;
-    status[i] = 1;
-    jobs.push_back(Une8Job{stream[i], len[i], out[i], cap[i], nullptr});
-  }
-  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: no device");
-  std::string note;
-  const int got = engine_e8e9_decode(args[1], lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
-  if (got < 0) fail(ZPQ_E_UNSUPPORTED, "decoding on the device unavailable: " + note);
-  for (uint32_t i = 0; i < n; ++i) outlen[i] = (size_t)jobs[i].out_len;       // (every size is reported, also when some buffer is too small)
-  if (got == 0) fail(ZPQ_E_OVERFLOW, "output buffer too small");
-  for (uint32_t i = 0; i < n; ++i) status[i] = jobs[i].status;
-  return ZPQ_OK;
-  ZPQ_CATCH
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        return xm[0] == '0' || args[1] < 4 || args[1] > 7 || (args[1] == 7 && args[0] > 4) ? "not an E8E9 method (args[1] 4 .. 7, the BWT at args[0] <= 4)" : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) {
+        return engine_e8e9_decode(args[1], lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+      });
 }
 
 uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }

@@ -1,6 +1,6 @@
 // Batch engine: owns the device, the HBM arena pool and the launch sequence
 // (init_arena -> code_*).  One process drives one GPU; callers are serialised.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <hip/hip_runtime_api.h>
 #include <sched.h>
@@ -22,7 +22,6 @@
 
 #include "../host/codegen.hpp"
 #include "kernels.h"
-#include "fragment_stitch.hpp"
 #include "launch_policy.hpp"
 #include "sa_kernels.h"
 #include "spec_loader.hpp"
@@ -38,86 +37,7 @@ __attribute__((constructor)) static void zpq_more_hardware_queues() { setenv("GP
 
 namespace zpq {
 
-#define HIP_CHECK(expr)                                                                       \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      int code_ = (e_ == hipErrorOutOfMemory) ? ZPQ_E_NOMEM : ZPQ_E_DEVICE;                   \
-      fail(code_, std::string(#expr) + ": " + hipGetErrorString(e_));                         \
-    }                                                                                         \
-  } while (0)
-
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = (n + ((size_t)1 << 21) - 1) & ~(((size_t)1 << 21) - 1);
-    HIP_CHECK(hipMalloc(&p, want));
-    cap = want;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-// Page-locked host memory (ZPAQ_AMD_PINNED_STAGE): the staging buffer of host-buffer batches, DMA-able at link speed
-struct HostPinned {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t n) {                 // false: not available (the caller stages through pageable memory)
-    if (n <= cap) return true;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    size_t want = (n + ((size_t)1 << 21) - 1) & ~(((size_t)1 << 21) - 1);
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-
-// hipEvent_t that cannot leak when a HIP_CHECK throws between create and destroy
-struct Event {
-  hipEvent_t ev = nullptr;
-  explicit Event(bool timing = false) {
-    HIP_CHECK(hipEventCreateWithFlags(&ev, timing ? hipEventDefault : hipEventDisableTiming));
-  }
-  ~Event() { if (ev) (void)hipEventDestroy(ev); }
-  Event(const Event&) = delete;
-  Event& operator=(const Event&) = delete;
-  operator hipEvent_t() const { return ev; }
-};
-
-struct Engine {
-  std::mutex mu;
-  bool ready = false;
-  int device = -1;                     // HIP device this engine drives
-  int slot = 0;                        // its index in g_engines = the slot of every plan's per-engine state (zpq_plan::dev[])
-  hipStream_t stream = nullptr;
-  DeviceTables* d_tables = nullptr;
-  uint64_t budget = 0;
-  unsigned sharers = 1;          // engines configured on this engine's physical device (ZPAQ_AMD_DEVICES may name one twice)
-  int kernel_choice = 0;
-  DevBuf arena, io_in, io_out, jobs, results;
-  DevBuf segs;                         // segment tables of multi-segment blocks
-  DevBuf sha_jobs, sha_out;            // SHA-1 of the staged inputs (sha1_blocks_kernel)
-  DevBuf pipe;                         // stream buffers of the pipelined encoder (device/pipe_kernel.h)
-  DevBuf pipe_ctl;                     // the persistent launch's progress counters, chunk counts and abort words (device/pipe_persist.h)
-  HostPinned pin_in;                   // page-locked staging of host inputs, kept between calls (ZPAQ_AMD_PINNED_STAGE=0: pageable)
-  HostPinned pin_out;                  // ... and of the outputs of a large batch
-  hipStream_t pstream[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // one per pipe kernel
-  std::vector<hipStream_t> side;       // extra streams: independent launch groups run concurrently
-  Timing last{};
-  int last_kind = 0;
-  bool last_persist = false;           // the last batch's pipelined groups ran as persistent launches
-  double last_persist_abort_ms = 0.0;  // ... or: how long it took until a persistent launch of the last batch was given up (0: none was)
-  int jit_left = 0;                    // hipRTC compilations still allowed in the current call
-  std::atomic<int> cus{256};           // compute units of the device (atomic: the submission queue reads the primary engine's without its lock)
-  int xcds = 8;                        // ... and its compute dies
-  DeviceShape shape() const { return DeviceShape{cus.load(), xcds}; }
-  hipEvent_t busy = nullptr;           // recorded after the last launch of a call that returned with work in flight
-};
 
 // One engine per configured GPU, each in its own SLOT of g_engines.  `primary` serves the device-resident entry points
 // and every batch when only one engine is configured; host-buffer batches are sharded over `ids` (the slots in use:
@@ -153,11 +73,6 @@ int primary_device() {
   return d.primary;
 }
 
-Engine& eng(int slot = -1) {
-  if (slot < 0) slot = primary_device();
-  return g_engines[slot];
-}
-
 int device_of_slot(int slot) {
   DeviceSet& d = devset();
   std::lock_guard<std::mutex> g(d.mu);
@@ -169,7 +84,6 @@ void bind_slot(int device, int slot) {
   HIP_CHECK(hipSetDevice(device));
   set_plan_device_index(slot);
 }
-void bind_device(Engine& e) { bind_slot(e.device, e.slot); }
 
 // hipRTC compilations one call may spend on headers nobody compiled before (the rest of that call's unseen headers
 // run on the generic kernel and are picked up by later calls), and the host threads that compile side by side
@@ -182,12 +96,18 @@ int jit_threads() {
 }
 
 void engine_init_device(Engine& e, int slot, int device);
-void require_ready(Engine& e, int slot = -1) {
+
+}  // namespace
+
+Engine& engine_detail::eng(int slot) {
+  if (slot < 0) slot = primary_device();
+  return g_engines[slot];
+}
+void engine_detail::bind_device(Engine& e) { bind_slot(e.device, e.slot); }
+void engine_detail::require_ready(Engine& e, int slot) {
   if (slot < 0) slot = primary_device();
   if (!e.ready) engine_init_device(e, slot, device_of_slot(slot));          // lazy default init
 }
-
-}  // namespace
 
 namespace {
 void engine_init_device(Engine& e, int slot, int device) {
@@ -588,7 +508,7 @@ static bool launch_pipe_persist(Engine& e, const LaunchKnobs& knobs, std::vector
   for (size_t i = 0; i < runs.size(); ++i) {
     base[i] = words;
     words += 4 + runs[i].ngroups + (uint64_t)runs[i].ngroups * runs[i].ps_nunit;
-    words = (words + 63) & ~63ull;
+    words = align_up(words, 64);
   }
   e.pipe_ctl.ensure(words * 4);
   std::vector<uint32_t> host(words, 0);
@@ -940,7 +860,7 @@ static void launch_all(Engine& e, bool decode, const BlockJob* d_jobs, BlockResu
 
 // The engine's arena / job / stream buffers are shared by all calls: a call that returned with work still in flight
 // on the caller's stream (zpq_*_device with timed = 0) must have drained before they are touched again.
-static void wait_in_flight(Engine& e) {
+void engine_detail::wait_in_flight(Engine& e) {
   if (e.busy) {
     HIP_CHECK(hipEventSynchronize(e.busy));
   }
@@ -1174,11 +1094,8 @@ void engine_code_host_now(bool decode, const std::vector<HostBlock>& blocks, std
 }
 
 void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blocks, std::vector<BlockResult>& results) {
-  Engine& e = eng(dev);
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e, dev);
-  bind_device(e);
-  wait_in_flight(e);
+  EngineCall call(dev);
+  Engine& e = call.e;
   const size_t nb = blocks.size();
   const LaunchKnobs knobs = launch_knobs();
   e.jit_left = jit_budget();
@@ -1204,8 +1121,8 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
       if (end > pos && need + a > e.budget) break;
       need += a;
       max_arena = std::max(max_arena, hb.plan->hdr().arena_bytes);
-      in_bytes += ((uint64_t)hb.in_len + hb.prefix_len + 63) & ~63ull;
-      out_bytes += ((uint64_t)hb.out_cap + 63) & ~63ull;
+      in_bytes += align_up((uint64_t)hb.in_len + hb.prefix_len, 64);
+      out_bytes += align_up(hb.out_cap, 64);
       ++end;
     }
     if (need > e.budget) fail(ZPQ_E_NOMEM, "Out of memory: one block's model state exceeds the device budget");
@@ -1279,8 +1196,8 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
       in_off_of[k] = i_off;
       out_off[k] = o_off;
       a_off += hb.plan->hdr().arena_bytes;
-      i_off += ((uint64_t)hb.in_len + hb.prefix_len + 63) & ~63ull;
-      o_off += ((uint64_t)hb.out_cap + 63) & ~63ull;
+      i_off += align_up((uint64_t)hb.in_len + hb.prefix_len, 64);
+      o_off += align_up(hb.out_cap, 64);
     }
     // Gather + copy.  The pipelined encoder reads input byte k no earlier than step k / chunk, so for a batch of equally long
     // blocks (the bulk case: compress() / compressBlocks over a cut-up stream) only the first kHeadBytes of every block are
@@ -1292,7 +1209,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
     if (const char* sc = getenv("ZPAQ_AMD_SPLIT_COPY")) split = split && sc[0] != '0';      // (A/B aid: "0" = one copy up front)
     for (size_t k = 0; split && k < cnt; ++k)
       split = blocks[order[k]].in_len + blocks[order[k]].prefix_len == len0 && kind_of_sorted(groups, k) == 4;
-    const uint64_t pitch = ((uint64_t)len0 + 63) & ~63ull;      // (= the distance between two blocks' inputs when all are len0 long)
+    const uint64_t pitch = align_up(len0, 64);      // (= the distance between two blocks' inputs when all are len0 long)
     // bytes [from, to) of every block's input (prefix first, then the data) -> staging
     auto gather_range = [&](size_t t, size_t nt, uint32_t from, uint32_t to) {
       for (size_t k = t; k < cnt; k += nt) {
@@ -1422,7 +1339,7 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
       const HostBlock& hb = blocks[order[k]];
       results[order[k]] = res[k];
       pin_off[k] = out_total;
-      if (hb.out) out_total += ((uint64_t)std::min(res[k].out_len, hb.out_cap) + 15) & ~15ull;
+      if (hb.out) out_total += align_up(std::min(res[k].out_len, hb.out_cap), 16);
     }
     const bool pin_outputs = pinned && cnt >= 64 && out_total >= (1u << 20) && e.pin_out.ensure(out_total + 64);
     for (size_t k = 0; k < cnt; ++k) {
@@ -1469,11 +1386,8 @@ void engine_code_host_on(int dev, bool decode, const std::vector<HostBlock>& blo
 void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan, const void* d_in,
                         const uint64_t* in_off, const uint32_t* in_len, uint32_t nblocks, void* d_out,
                         const uint64_t* out_off, const uint32_t* out_cap, BlockResult* d_res, void* stream, bool timed) {
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
+  EngineCall call;
+  Engine& e = call.e;
   hipStream_t st = stream ? (hipStream_t)stream : e.stream;
   const LaunchKnobs knobs = launch_knobs();
   e.jit_left = jit_budget();
@@ -1518,906 +1432,6 @@ void engine_code_device(bool decode, const zpq_plan* const* plans, bool one_plan
   if (!timed) mark_in_flight(e, st);
 }
 
-bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note, bool* handed_back) {
-  if (handed_back) *handed_back = false;
-  if (segs.empty()) return true;
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  PcompKernel* k = pcomp_kernel_for(code, codelen, ph, pm, note);
-  if (!k) return false;
-  if (handed_back) *handed_back = true;          // (every false from here on)
-  const size_t n = segs.size();
-  const uint64_t mbytes = ((1ull << pm) + 255) & ~255ull, hbytes = ((4ull << ph) + 255) & ~255ull;
-  std::vector<uint64_t> cap(n);
-  for (size_t i = 0; i < n; ++i) cap[i] = (segs[i].hint ? segs[i].hint : 8ull * segs[i].in_len) + 65536;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    uint64_t in_bytes = 0, out_bytes = 0;
-    for (size_t i = 0; i < n; ++i) {
-      if (cap[i] > 0xFFFFFFF0ull) { note = "segment output beyond the device kernel's 32-bit range"; return false; }   // the host runs it (the size hint is a comment the reference ignores)
-      in_bytes += ((uint64_t)segs[i].in_len + 63) & ~63ull;
-      out_bytes += (cap[i] + 63) & ~63ull;
-    }
-    const uint64_t work = (uint64_t)n * (mbytes + hbytes + 1024);
-    if (in_bytes + out_bytes + work > e.budget) { note = "post-processor state exceeds the device budget"; return false; }
-    e.io_in.ensure(in_bytes + 64);
-    e.io_out.ensure(out_bytes + 64);
-    e.arena.ensure(work);
-    e.jobs.ensure(n * sizeof(PcompJob));
-    e.results.ensure(n * 8);
-    std::vector<uint8_t> stage(in_bytes + 64);
-    std::vector<PcompJob> jobs(n);
-    std::vector<uint64_t> ooff(n);
-    uint64_t io = 0, oo = 0;
-    for (size_t i = 0; i < n; ++i) {
-      if (segs[i].in_len) memcpy(stage.data() + io, segs[i].in, segs[i].in_len);
-      PcompJob& j = jobs[i];
-      j.in = (const uint8_t*)e.io_in.p + io;
-      j.out = (uint8_t*)e.io_out.p + oo;
-      uint8_t* w = (uint8_t*)e.arena.p + (uint64_t)i * (mbytes + hbytes + 1024);
-      j.M = w;
-      j.H = (uint32_t*)(w + mbytes);
-      j.R = (uint32_t*)(w + mbytes + hbytes);
-      j.in_len = segs[i].in_len;
-      j.out_cap = (uint32_t)cap[i];
-      j.result = (uint32_t*)e.results.p + 2 * i;
-      ooff[i] = oo;
-      io += ((uint64_t)segs[i].in_len + 63) & ~63ull;
-      oo += (cap[i] + 63) & ~63ull;
-    }
-    HIP_CHECK(hipMemsetAsync(e.arena.p, 0, work, e.stream));
-    HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(e.jobs.p, jobs.data(), n * sizeof(PcompJob), hipMemcpyHostToDevice, e.stream));
-    const PcompJob* d_jobs = (const PcompJob*)e.jobs.p;
-    unsigned nn = (unsigned)n;
-    void* args[2] = {(void*)&d_jobs, (void*)&nn};
-    HIP_CHECK(hipModuleLaunchKernel(k->fn, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, e.stream, args, nullptr));
-    std::vector<uint32_t> res(2 * n);
-    HIP_CHECK(hipMemcpyAsync(res.data(), e.results.p, n * 8, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    bool again = false;
-    for (size_t i = 0; i < n; ++i) {
-      // a device status is not a verdict: the translated program has a fixed budget of backward jumps, so the host
-      // post-processor (which owns the ZPAQL-error decision, like the reference's) runs these segments again
-      if (res[2 * i + 1]) { note = "device post-processor stopped (status " + std::to_string(res[2 * i + 1]) + "): host fallback"; return false; }
-      if (res[2 * i] > cap[i]) { cap[i] = res[2 * i]; again = true; }
-    }
-    if (again && attempt == 0) continue;
-    for (size_t i = 0; i < n; ++i) {
-      segs[i].out->resize(res[2 * i]);
-      if (res[2 * i])
-        HIP_CHECK(hipMemcpyAsync(segs[i].out->data(), (const uint8_t*)e.io_out.p + ooff[i], res[2 * i], hipMemcpyDeviceToHost, e.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    return true;
-  }
-  return false;
-}
-
-// SHA-1 of n host buffers on the device (one lane per buffer); 20 bytes each into out.
-void engine_sha1_host(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint8_t* out) {
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  uint64_t bytes = 0;
-  for (uint32_t i = 0; i < n; ++i) bytes += ((uint64_t)len[i] + 63) & ~63ull;
-  e.io_in.ensure(bytes + 64);
-  e.sha_jobs.ensure((size_t)n * sizeof(Sha1Job));
-  e.sha_out.ensure((size_t)n * 20);
-  std::vector<uint8_t> stage(bytes + 64);
-  std::vector<Sha1Job> jobs(n);
-  uint64_t off = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (len[i]) memcpy(stage.data() + off, in[i], len[i]);
-    jobs[i] = Sha1Job{(const uint8_t*)e.io_in.p + off, len[i], i};
-    off += ((uint64_t)len[i] + 63) & ~63ull;
-  }
-  HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.data(), bytes, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(e.sha_jobs.p, jobs.data(), (size_t)n * sizeof(Sha1Job), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(launch_sha1((const Sha1Job*)e.sha_jobs.p, n, (uint8_t*)e.sha_out.p, e.stream));
-  HIP_CHECK(hipMemcpyAsync(out, e.sha_out.p, (size_t)n * 20, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-}
-
-bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, std::vector<std::vector<U32>>& sa, std::string& note) {
-  const size_t n = blocks.size();
-  sa.assign(n, std::vector<U32>());
-  uint64_t total = 0;
-  uint32_t max_len = 0;
-  for (auto& b : blocks) { total += b.second; max_len = std::max(max_len, b.second); }
-  if (!total) return true;
-  if (n > 65535 || max_len >= (1u << 24) || total >= (1ull << 31)) { note = "batch outside the device sorter's range"; return false; }
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  const size_t ws = sa_workspace_bytes(total, (uint32_t)n);
-  const uint64_t in_bytes = (total + 255) & ~255ull;
-  if (ws + in_bytes + 4 * total + (1u << 20) > e.budget) { note = "suffix sort workspace exceeds the device budget"; return false; }
-  // inputs back to back in io_in, the arrays in io_out, the sorter's workspace in the arena buffer (idle between batches)
-  e.io_in.ensure(in_bytes + 64);
-  e.io_out.ensure(4 * total + 64);
-  e.arena.ensure(ws);
-  e.jobs.ensure((n + 2) * 16 + 64);
-  std::vector<const uint8_t*> ptrs(n);
-  std::vector<uint64_t> off(n + 1, 0);
-  const bool pinned = in_bytes >= (1u << 20) && e.pin_in.ensure(in_bytes + 64);
-  std::unique_ptr<uint8_t[]> pageable;
-  uint8_t* stage = pinned ? (uint8_t*)e.pin_in.p : (pageable.reset(new uint8_t[in_bytes + 64]), pageable.get());
-  for (size_t i = 0; i < n; ++i) {
-    ptrs[i] = (const uint8_t*)e.io_in.p + off[i];
-    if (blocks[i].second) memcpy(stage + off[i], blocks[i].first, blocks[i].second);
-    off[i + 1] = off[i] + blocks[i].second;
-  }
-  uint8_t* meta = (uint8_t*)e.jobs.p;
-  HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage, total, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(meta, ptrs.data(), n * 8, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(meta + ((n * 8 + 15) & ~15ull), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, e.stream));
-  uint32_t rounds = 0;
-  const hipError_t rc = build_suffix_arrays((const uint8_t* const*)meta, (const uint64_t*)(meta + ((n * 8 + 15) & ~15ull)), (uint32_t)n, total, max_len,
-                                            (uint32_t*)e.io_out.p, e.arena.p, e.arena.cap, e.stream, &rounds);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device suffix sort failed: ") + hipGetErrorString(rc); return false; }
-  for (size_t i = 0; i < n; ++i) {
-    sa[i].resize(blocks[i].second);
-    if (blocks[i].second)
-      HIP_CHECK(hipMemcpyAsync(sa[i].data(), (const uint32_t*)e.io_out.p + off[i], 4ull * blocks[i].second, hipMemcpyDeviceToHost, e.stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  note = "device, " + std::to_string(rounds) + " doubling rounds";
-  return true;
-}
-
-// Stages (c) and (d) of device/lz77_codes_kernel.h, behind launch_lz77_code_lengths on e.stream: the sizes and the error word come
-// back, the streams are placed back to back (every start on a word) in the `room` bytes at d_out, emitted there and downloaded
-// into dst[b] (null: not a block of kind 1 / 2).  Sizes first, then emission: a degenerate list can expand a block, no bound is
-// guessed.  false + note: a list the host's coder refuses or an incomplete one (*refused says which), or no room.
-namespace {
-bool finish_lz77_codes(Engine& e, const std::vector<LzBlock>& blk, const uint8_t* d_in, uint64_t total, const LzBlock* d_blk, const LzTok* d_toks,
-                       const uint32_t* d_counts, const LzCodes& c, uint64_t* d_ooff, uint8_t* d_out, uint64_t room,
-                       const std::vector<std::vector<U8>*>& dst, std::string& note, uint32_t* refused) {
-  const size_t n = blk.size();
-  std::vector<uint32_t> sizes(n + 1);
-  HIP_CHECK(hipMemcpyAsync(sizes.data(), c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  if (refused) *refused = sizes[n];
-  if (sizes[n]) { note = (sizes[n] & kLzcErrList) ? "LZ77 token list refused by the coder's checks" : "LZ77 token list overflowed"; return false; }
-  std::vector<uint64_t> ooff(n + 1, 0);
-  for (size_t i = 0; i < n; ++i) ooff[i + 1] = ooff[i] + (((uint64_t)sizes[i] + 3) & ~3ull);
-  if (ooff[n] > room) { note = "the coded streams do not fit the device's output buffer"; return false; }
-  if (!ooff[n]) return true;
-  HIP_CHECK(hipMemcpyAsync(d_ooff, ooff.data(), 8 * (n + 1), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemsetAsync(d_out, 0, ooff[n], e.stream));
-  const hipError_t rc = launch_lz77_emit(d_in, d_blk, (uint32_t)n, total, d_toks, d_counts, c, d_ooff, d_out, e.stream);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 coder failed: ") + hipGetErrorString(rc); return false; }
-  for (size_t i = 0; i < n; ++i) {
-    if (!dst[i]) continue;
-    dst[i]->resize(sizes[i]);
-    if (sizes[i]) HIP_CHECK(hipMemcpyAsync(dst[i]->data(), d_out + ooff[i], sizes[i], hipMemcpyDeviceToHost, e.stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  return true;
-}
-// codes == 2: does writing the codes here pay for this batch?  The sizes and the counts are on the device behind the walk.
-bool codes_pay(Engine& e, const std::vector<LzBlock>& blk, const LzCodes& c, const uint32_t* d_counts, uint64_t total) {
-  const size_t n = blk.size();
-  std::vector<uint32_t> sizes(n + 1), cnt(n);
-  HIP_CHECK(hipMemcpyAsync(sizes.data(), c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipMemcpyAsync(cnt.data(), d_counts, 4 * n, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  if (sizes[n]) return true;                         // (the error word: finish_lz77_codes reports it)
-  uint64_t matches = 0, bytes = 0;
-  for (size_t i = 0; i < n; ++i) { matches += cnt[i]; bytes += sizes[i]; }
-  return lz_codes_pay(matches, bytes, total);
-}
-// the coder's share of a parse call's output buffer, behind `at`: sizes + error word, the streams' places, lengths / offsets, scan scratch
-struct CodesLayout { uint64_t o_sizes, o_ooff, o_pos, o_tmp, end; LzCodes c; };
-CodesLayout codes_layout(uint64_t at, size_t n, uint64_t nslots) {
-  CodesLayout L;
-  L.o_sizes = (at + 255) & ~255ull;
-  L.o_ooff = (L.o_sizes + 4 * (n + 1) + 255) & ~255ull;
-  L.o_pos = (L.o_ooff + 8 * (n + 1) + 255) & ~255ull;
-  L.o_tmp = (L.o_pos + 8 * (nslots + 1) + 255) & ~255ull;
-  L.c.nslots = nslots;
-  L.c.tmp_bytes = lzc_scan_bytes(nslots);
-  L.end = L.o_tmp + L.c.tmp_bytes;
-  return L;
-}
-void codes_bind(CodesLayout& L, uint8_t* base) {
-  L.c.pos = (uint64_t*)(base + L.o_pos);
-  L.c.tmp = base + L.o_tmp;
-  L.c.sizes = (uint32_t*)(base + L.o_sizes);
-}
-}  // namespace
-
-bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes) {
-  const size_t n = jobs.size();
-  out.assign(n, SortOut());
-  uint64_t total = 0, ntok = 0, bwt_bytes = 0;
-  uint32_t max_len = 0;
-  bool any_lz = false, any_bwt = false;
-  std::vector<LzBlock> blk(n);
-  for (size_t i = 0; i < n; ++i) {
-    const SortJob& j = jobs[i];
-    LzBlock& B = blk[i];
-    memset(&B, 0, sizeof(B));
-    B.off = total;
-    B.n = j.n;
-    B.kind = j.n ? j.kind : 0u;
-    B.min_match = j.min_match; B.lookahead = j.lookahead; B.bucket = j.bucket; B.checkbits = j.checkbits;
-    B.rb = j.rb;
-    B.tok_off = ntok;                                // (every block: the coder's item slots are found by it)
-    if (B.kind == 1 || B.kind == 2) {
-      if (j.min_match < 1 || j.lookahead > 255 || j.checkbits < 1 || j.checkbits > 31) { note = "LZ77 parameters outside the device parser's range"; return false; }
-      B.tok_cap = j.n / j.min_match + 2;
-      ntok += B.tok_cap;
-      any_lz = true;
-    } else if (B.kind == 3) {
-      any_bwt = true;
-    } else if (B.kind != 0) { note = "unknown pre-processor kind"; return false; }
-    total += j.n;
-    max_len = std::max(max_len, j.n);
-  }
-  if (!total) return true;
-  bwt_bytes = any_bwt ? total + n : 0;
-  if (n > 65535 || max_len >= (1u << 24) || total >= (1ull << 31)) { note = "batch outside the device sorter's range"; return false; }
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  const size_t ws = sa_workspace_bytes(total, (uint32_t)n);
-  const uint64_t in_bytes = (total + 255) & ~255ull;
-  // behind the arrays in io_out: decisions (16 B per element), tokens, BWT bytes, counts and indices, the block table
-  const uint64_t o_res = (4 * total + 255) & ~255ull;
-  const uint64_t o_tok = o_res + (any_lz ? 16 * total : 0);
-  const uint64_t o_bwt = o_tok + 16 * ntok;
-  const uint64_t o_cnt = (o_bwt + bwt_bytes + 255) & ~255ull;
-  const uint64_t o_idx = o_cnt + 4 * n;
-  const uint64_t o_blk = (o_idx + 4 * n + 255) & ~255ull;
-  if (!any_lz) codes = 0;
-  // ... and the coder's arrays (device/lz77_codes_kernel.h); the streams themselves take the place of the decisions, which are
-  // dead behind the walk
-  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
-  const uint64_t out_bytes = (codes ? cl.end : o_blk + n * sizeof(LzBlock)) + 256;
-  if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "sort + parse workspace exceeds the device budget"; return false; }
-  e.io_in.ensure(in_bytes + 64);
-  e.io_out.ensure(out_bytes);
-  e.arena.ensure(ws);
-  e.jobs.ensure((n + 2) * 16 + 64);
-  std::vector<const uint8_t*> ptrs(n);
-  std::vector<uint64_t> off(n + 1, 0);
-  const bool pinned = in_bytes >= (1u << 20) && e.pin_in.ensure(in_bytes + 64);
-  std::unique_ptr<uint8_t[]> pageable;
-  uint8_t* stage = pinned ? (uint8_t*)e.pin_in.p : (pageable.reset(new uint8_t[in_bytes + 64]), pageable.get());
-  for (size_t i = 0; i < n; ++i) {
-    ptrs[i] = (const uint8_t*)e.io_in.p + off[i];
-    if (jobs[i].n) memcpy(stage + off[i], jobs[i].data, jobs[i].n);
-    off[i + 1] = off[i] + jobs[i].n;
-  }
-  uint8_t* meta = (uint8_t*)e.jobs.p;
-  uint8_t* const ob = (uint8_t*)e.io_out.p;
-  HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage, total, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(meta, ptrs.data(), n * 8, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(meta + ((n * 8 + 15) & ~15ull), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 8 * n, e.stream));
-  if (codes) { codes_bind(cl, ob); HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream)); }
-  uint32_t rounds = 0;
-  SaSideArrays side;
-  hipError_t rc = build_suffix_arrays((const uint8_t* const*)meta, (const uint64_t*)(meta + ((n * 8 + 15) & ~15ull)), (uint32_t)n, total, max_len,
-                                      (uint32_t*)ob, e.arena.p, e.arena.cap, e.stream, &rounds, &side);
-  if (rc == hipSuccess)
-    rc = launch_sort_preprocessors((const uint8_t*)e.io_in.p, (const uint32_t*)ob, side, (const LzBlock*)(ob + o_blk), (uint32_t)n, total, any_lz, any_bwt,
-                                   ob + o_res, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), ob + o_bwt, (uint32_t*)(ob + o_idx), e.stream,
-                                   codes ? &cl.c : nullptr);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device sort / parse failed: ") + hipGetErrorString(rc); return false; }
-  if (codes == 2 && !codes_pay(e, blk, cl.c, (const uint32_t*)(ob + o_cnt), total)) codes = 0;     // (the lists come back, as without the coder)
-  if (codes) {
-    std::vector<std::vector<U8>*> dst(n, nullptr);
-    for (size_t i = 0; i < n; ++i)
-      if (blk[i].kind == 1 || blk[i].kind == 2) { dst[i] = &out[i].codes; out[i].coded = true; }
-    if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ob + o_blk), (const LzTok*)(ob + o_tok), (const uint32_t*)(ob + o_cnt),
-                           cl.c, (uint64_t*)(ob + cl.o_ooff), ob + o_res, 16 * total, dst, note, nullptr))
-      return false;
-  }
-  std::vector<uint32_t> cnt(2 * n);
-  HIP_CHECK(hipMemcpyAsync(cnt.data(), ob + o_cnt, 8 * n, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  static_assert(sizeof(LzTok) == sizeof(LzToken) && sizeof(LzTok) == 16, "token layouts");
-  for (size_t i = 0; i < n; ++i) {
-    const LzBlock& B = blk[i];
-    if (B.kind == 1 || B.kind == 2) {
-      if (codes) continue;                                          // (its stream is there already)
-      if (cnt[i] > B.tok_cap) { note = "LZ77 token list overflowed"; return false; }
-      out[i].toks.resize(cnt[i]);
-      if (cnt[i]) HIP_CHECK(hipMemcpyAsync(out[i].toks.data(), ob + o_tok + 16 * B.tok_off, 16ull * cnt[i], hipMemcpyDeviceToHost, e.stream));
-    } else if (B.kind == 3) {
-      out[i].bwt.resize((size_t)B.n + 5);
-      HIP_CHECK(hipMemcpyAsync(out[i].bwt.data(), ob + o_bwt + B.off + i, (size_t)B.n + 1, hipMemcpyDeviceToHost, e.stream));
-      uint32_t idx = cnt[n + i];
-      for (int k = 0; k < 4; ++k) { out[i].bwt[(size_t)B.n + 1 + k] = (U8)idx; idx >>= 8; }
-    }
-  }
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  note = "device, " + std::to_string(rounds) + " doubling rounds";
-  return true;
-}
-
-bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes) {
-  const size_t n = jobs.size();
-  out.assign(n, SortOut());
-  uint64_t total = 0, ntok = 0, nkeys = 0, nidx = 0;
-  std::vector<LzBlock> blk(n);
-  for (size_t i = 0; i < n; ++i) {
-    const SortJob& j = jobs[i];
-    if (!hash_job_in_range(j)) { note = "LZ77 parameters or block size outside the device hash parser's range"; return false; }
-    LzBlock& B = blk[i];
-    memset(&B, 0, sizeof(B));
-    B.off = total;
-    B.n = j.n;
-    B.kind = j.n ? j.kind : 0u;
-    B.min_match = j.min_match; B.lookahead = j.lookahead; B.bucket = j.bucket; B.checkbits = j.checkbits;
-    B.min_match2 = j.min_match2; B.ht_bits = j.ht_bits;
-    B.rb = j.rb;
-    B.tok_off = ntok;
-    B.tok_cap = j.n / j.min_match + 2;
-    ntok += B.tok_cap;
-    lz_hash_plan(B, nkeys, nidx);
-    total += j.n;
-  }
-  if (!total) return true;
-  if (n > 65535 || total >= (1ull << 31)) { note = "batch outside the device hash parser's range"; return false; }
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  const size_t ws = lzh_workspace_bytes(total, nkeys, nidx);
-  const uint64_t in_bytes = (total + 255) & ~255ull;
-  // io_out: decisions (16 B per element), tokens, counts, the block table
-  const uint64_t o_tok = 16 * total;
-  const uint64_t o_cnt = (o_tok + 16 * ntok + 255) & ~255ull;
-  const uint64_t o_blk = (o_cnt + 4 * n + 255) & ~255ull;
-  // ... and the coder's arrays; the streams take the place of the decisions (device/lz77_codes_kernel.h)
-  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
-  const uint64_t out_bytes = (codes ? cl.end : o_blk + n * sizeof(LzBlock)) + 256;
-  if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "hash parse workspace exceeds the device budget"; return false; }
-  e.io_in.ensure(in_bytes + 64);
-  e.io_out.ensure(out_bytes);
-  e.arena.ensure(ws);
-  const bool pinned = in_bytes >= (1u << 20) && e.pin_in.ensure(in_bytes + 64);
-  std::unique_ptr<uint8_t[]> pageable;
-  uint8_t* stage = pinned ? (uint8_t*)e.pin_in.p : (pageable.reset(new uint8_t[in_bytes + 64]), pageable.get());
-  for (size_t i = 0; i < n; ++i)
-    if (jobs[i].n) memcpy(stage + blk[i].off, jobs[i].data, jobs[i].n);
-  uint8_t* const ob = (uint8_t*)e.io_out.p;
-  HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage, total, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 4 * n, e.stream));
-  if (codes) { codes_bind(cl, ob); HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream)); }
-  const hipError_t rc = launch_hash_parse((const uint8_t*)e.io_in.p, (const LzBlock*)(ob + o_blk), (uint32_t)n, total, nkeys, nidx, e.arena.p, e.arena.cap,
-                                          ob, (LzTok*)(ob + o_tok), (uint32_t*)(ob + o_cnt), e.stream, codes ? &cl.c : nullptr);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device hash parse failed: ") + hipGetErrorString(rc); return false; }
-  if (codes == 2 && !codes_pay(e, blk, cl.c, (const uint32_t*)(ob + o_cnt), total)) codes = 0;     // (the lists come back, as without the coder)
-  if (codes) {
-    std::vector<std::vector<U8>*> dst(n, nullptr);
-    for (size_t i = 0; i < n; ++i)
-      if (blk[i].kind == 1 || blk[i].kind == 2) { dst[i] = &out[i].codes; out[i].coded = true; }
-    if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ob + o_blk), (const LzTok*)(ob + o_tok), (const uint32_t*)(ob + o_cnt),
-                           cl.c, (uint64_t*)(ob + cl.o_ooff), ob, 16 * total, dst, note, nullptr))
-      return false;
-    note = "device, " + std::to_string(nkeys) + " keys, coded there";
-    return true;
-  }
-  std::vector<uint32_t> cnt(n);
-  HIP_CHECK(hipMemcpyAsync(cnt.data(), ob + o_cnt, 4 * n, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  for (size_t i = 0; i < n; ++i) {
-    const LzBlock& B = blk[i];
-    if (cnt[i] > B.tok_cap) { note = "LZ77 token list overflowed"; return false; }
-    out[i].toks.resize(cnt[i]);
-    if (cnt[i]) HIP_CHECK(hipMemcpyAsync(out[i].toks.data(), ob + o_tok + 16 * B.tok_off, 16ull * cnt[i], hipMemcpyDeviceToHost, e.stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  note = "device, " + std::to_string(nkeys) + " keys";
-  return true;
-}
-
-int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<U8>>& out, std::string& note) {
-  const size_t n = jobs.size();
-  out.assign(n, std::vector<U8>());
-  if (!n) return 1;
-  uint64_t total = 0, ntok = 0;
-  std::vector<LzBlock> blk(n);
-  std::vector<uint32_t> cnt(n);
-  bool in_range = n <= 65535;
-  for (size_t i = 0; i < n && in_range; ++i) {
-    const CodeJob& j = jobs[i];
-    in_range = j.n < (1u << 24) && (j.kind == 1 || j.kind == 2) && j.min_match >= 1 && j.min_match <= 255 && j.rb <= 7 && j.ntok <= (size_t)j.n + 1;
-    LzBlock& B = blk[i];
-    memset(&B, 0, sizeof(B));
-    B.off = total;
-    B.n = j.n;
-    B.kind = j.kind;                                 // (also for an empty block: a list over it must be refused)
-    B.min_match = j.min_match;
-    B.rb = j.rb;
-    B.tok_off = ntok;
-    B.tok_cap = cnt[i] = (uint32_t)j.ntok;
-    ntok += j.ntok;
-    total += j.n;
-  }
-  // (a list of more than n + 1 tokens cannot be in order: positions rise strictly -- but saying so is the kernel's job; such a
-  // list is merely outside what the buffers are sized for)
-  if (!in_range || total >= (1ull << 31)) { note = "batch outside the device coder's range"; return -1; }
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  // the arena buffer (idle between batches): tokens, counts, the block table, the coder's arrays; inputs in io_in, streams in io_out
-  const uint64_t o_cnt = (16 * ntok + 255) & ~255ull;
-  const uint64_t o_blk = (o_cnt + 4 * n + 255) & ~255ull;
-  CodesLayout cl = codes_layout(o_blk + n * sizeof(LzBlock), n, ntok + n);
-  const uint64_t ws = cl.end + 256, in_bytes = (total + 255) & ~255ull;
-  if (ws + in_bytes + (1u << 20) > e.budget) { note = "coder workspace exceeds the device budget"; return -1; }
-  e.io_in.ensure(in_bytes + 64);
-  e.arena.ensure(ws);
-  uint8_t* const ab = (uint8_t*)e.arena.p;
-  codes_bind(cl, ab);
-  std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
-  std::vector<LzToken> toks(ntok + 1);
-  for (size_t i = 0; i < n; ++i) {
-    if (jobs[i].n) memcpy(stage.get() + blk[i].off, jobs[i].data, jobs[i].n);
-    if (jobs[i].ntok) memcpy(toks.data() + blk[i].tok_off, jobs[i].toks, 16 * jobs[i].ntok);
-  }
-  static_assert(sizeof(LzTok) == sizeof(LzToken) && sizeof(LzTok) == 16, "token layouts");
-  if (total) HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), total, hipMemcpyHostToDevice, e.stream));
-  if (ntok) HIP_CHECK(hipMemcpyAsync(ab, toks.data(), 16 * ntok, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(ab + o_cnt, cnt.data(), 4 * n, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(ab + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemsetAsync(cl.c.sizes, 0, 4 * (n + 1), e.stream));
-  const hipError_t rc = launch_lz77_code_lengths((const LzBlock*)(ab + o_blk), (uint32_t)n, (const LzTok*)ab, (const uint32_t*)(ab + o_cnt), cl.c, e.stream);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 coder failed: ") + hipGetErrorString(rc); return -1; }
-  // sizes first: the streams' room is claimed once they are known
-  std::vector<uint32_t> sizes(n + 1);
-  HIP_CHECK(hipMemcpyAsync(sizes.data(), cl.c.sizes, 4 * (n + 1), hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  if (sizes[n]) { note = "LZ77 token list refused by the coder's checks"; return 0; }
-  uint64_t room = 0;
-  for (size_t i = 0; i < n; ++i) room += ((uint64_t)sizes[i] + 3) & ~3ull;
-  if (ws + in_bytes + room + (1u << 20) > e.budget) { note = "the coded streams exceed the device budget"; return -1; }
-  e.io_out.ensure(room + 64);
-  std::vector<std::vector<U8>*> dst(n);
-  for (size_t i = 0; i < n; ++i) dst[i] = &out[i];
-  uint32_t refused = 0;
-  if (!finish_lz77_codes(e, blk, (const uint8_t*)e.io_in.p, total, (const LzBlock*)(ab + o_blk), (const LzTok*)ab, (const uint32_t*)(ab + o_cnt), cl.c,
-                         (uint64_t*)(ab + cl.o_ooff), (uint8_t*)e.io_out.p, room, dst, note, &refused))
-    return refused ? 0 : -1;
-  return 1;
-}
-
-// device/e8e9_kernel.h over blocks that lie in io_out, in place.  The caller placed them (offsets multiples of 16, the rooms rounded
-// up) and ensured une8_ws(..).bytes of io_out at ws_off (a multiple of 256) for the first half: the block table, the tiles' counts,
-// the statuses, the scan's scratch.  The list of seeds and breaks is sized from the two totals the host reads between the halves
-// and goes to io_in, whose content the caller needs no longer; `held` = what the batch holds besides it.  status[k] = 0: block k
-// is filtered; 1: a lane gave it up, its bytes are to be dropped.  false + note: nothing is to be delivered.
-struct E8Ws { uint64_t o_cnt, o_st, o_tmp, bytes; size_t tmp_bytes; };
-static E8Ws une8_ws(size_t m, uint64_t ntiles) {
-  E8Ws w;
-  w.o_cnt = (m * sizeof(E8Block) + 255) & ~255ull;
-  w.o_st = (w.o_cnt + 4 * (2 * ntiles + 1) + 255) & ~255ull;
-  w.o_tmp = (w.o_st + 4 * m + 255) & ~255ull;
-  w.tmp_bytes = une8_scan_bytes((uint32_t)ntiles);
-  w.bytes = w.o_tmp + w.tmp_bytes + 256;
-  return w;
-}
-static bool une8_run(Engine& e, uint64_t ws_off, const std::vector<E8Block>& blk, uint64_t ntiles, uint64_t held, std::vector<uint32_t>& status,
-                     std::string& note) {
-  const size_t m = blk.size();
-  status.assign(m, 1u);
-  if (!m) return true;
-  const E8Ws w = une8_ws(m, ntiles);
-  uint8_t* const ob = (uint8_t*)e.io_out.p;
-  uint8_t* const wb = ob + ws_off;
-  uint32_t* const cnt = (uint32_t*)(wb + w.o_cnt);
-  HIP_CHECK(hipMemcpyAsync(wb, blk.data(), m * sizeof(E8Block), hipMemcpyHostToDevice, e.stream));
-  hipError_t rc = launch_une8_mark(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)(wb + w.o_st), wb + w.o_tmp, w.tmp_bytes, e.stream);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device E8E9 filter failed: ") + hipGetErrorString(rc); return false; }
-  uint32_t nseeds = 0, nlist = 0;
-  HIP_CHECK(hipMemcpyAsync(&nseeds, cnt + ntiles, 4, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipMemcpyAsync(&nlist, cnt + 2 * ntiles, 4, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  if (nseeds) {
-    if (held + 4ull * nlist + (1u << 20) > e.budget) { note = "the filter's list exceeds the device budget"; return false; }
-    e.io_in.ensure(4ull * nlist + 64);
-    rc = launch_une8_walk(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)e.io_in.p, nseeds, kE8MaxSteps, (uint32_t*)(wb + w.o_st), e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device E8E9 filter failed: ") + hipGetErrorString(rc); return false; }
-  }
-  HIP_CHECK(hipMemcpyAsync(status.data(), wb + w.o_st, 4 * m, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  return true;
-}
-
-// device/lz77_decode_kernel.h for a batch of host streams: one upload, the parse, 12 bytes per stream back, the outputs placed
-// back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.  e8: the method's program filters
-// M before it writes it out -- the outputs are placed for device/e8e9_kernel.h, which runs over them before they go down.
-template <class Job>
-static int lz77_decode_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<Job>& jobs, std::string& note, bool e8) {
-  const size_t n = jobs.size();
-  if (!n) return 1;
-  for (Job& j : jobs) { j.status = 1; j.out_len = 0; }
-  if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
-  std::vector<UnlzStream> st(n);
-  uint64_t in_bytes = 0, ntok = 0;
-  for (size_t i = 0; i < n; ++i) {
-    UnlzStream& S = st[i];
-    memset(&S, 0, sizeof(S));
-    S.in_off = in_bytes;
-    S.tok_off = ntok;
-    S.in_len = jobs[i].in_len;
-    S.tok_cap = jobs[i].in_len;                      // a code has at least 8 bits: at most one token per stream byte
-    S.level = level;
-    S.rb = rb;
-    S.min_match = min_match;
-    S.mbits = mbits;
-    in_bytes += ((uint64_t)jobs[i].in_len + 3) & ~3ull;
-    ntok += jobs[i].in_len;
-  }
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  // the arena buffer (idle between batches): tokens, the stream table, the results, where the outputs start
-  const uint64_t o_st = (16 * ntok + 255) & ~255ull;
-  const uint64_t o_res = (o_st + n * sizeof(UnlzStream) + 255) & ~255ull;
-  const uint64_t o_off = (o_res + n * sizeof(UnlzResult) + 255) & ~255ull;
-  const uint64_t ws = o_off + 8 * n + 256;
-  if (ws + in_bytes + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return -1; }
-  e.io_in.ensure(in_bytes + 64);
-  e.arena.ensure(ws);
-  uint8_t* const ab = (uint8_t*)e.arena.p;
-  std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
-  for (size_t i = 0; i < n; ++i) {
-    uint8_t* at = stage.get() + st[i].in_off;
-    if (jobs[i].in_len) memcpy(at, jobs[i].in, jobs[i].in_len);
-    memset(at + jobs[i].in_len, 0, (size_t)((0u - jobs[i].in_len) & 3u));
-  }
-  if (in_bytes) HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), in_bytes, hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), n * sizeof(UnlzStream), hipMemcpyHostToDevice, e.stream));
-  hipError_t rc = launch_unlz_parse((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (UnlzResult*)(ab + o_res), e.stream);
-  if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); return -1; }
-  std::vector<UnlzResult> res(n);
-  HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, n * sizeof(UnlzResult), hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  std::vector<uint64_t> off(n);
-  uint64_t room = 0, tiles = 0;
-  bool fits = true, any = false;
-  std::vector<E8Block> fb;                          // e8: the decoded blocks as the filter sees them, fb[k] is jobs[fwho[k]]
-  std::vector<size_t> fwho;
-  for (size_t i = 0; i < n; ++i) {
-    off[i] = room;
-    if (res[i].status != kUnlzOk) continue;
-    jobs[i].out_len = res[i].out_len;
-    if (e8) {
-      fb.push_back(E8Block{room, res[i].out_len, (uint32_t)tiles});
-      fwho.push_back(i);
-      tiles += e8_tiles(res[i].out_len);
-    }
-    room += e8 ? e8_room(res[i].out_len) : res[i].out_len;
-    any = true;
-    if (!jobs[i].vec && res[i].out_len > jobs[i].cap) fits = false;
-  }
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Job& j : jobs) j.out_len = 0; return -1; }
-  const uint64_t f_off = e8 ? (room + 255) & ~255ull : room, f_ws = e8 ? une8_ws(fb.size(), tiles).bytes : 0;
-  if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; for (Job& j : jobs) j.out_len = 0; return -1; }
-  if (!fits) return 0;
-  std::vector<uint32_t> fst;
-  if (any) {
-    e.io_out.ensure(f_off + f_ws + 64);
-    HIP_CHECK(hipMemcpyAsync(ab + o_off, off.data(), 8 * n, hipMemcpyHostToDevice, e.stream));
-    rc = launch_unlz_copy((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (const UnlzResult*)(ab + o_res),
-                          (const uint64_t*)(ab + o_off), (uint8_t*)e.io_out.p, e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device LZ77 decoder failed: ") + hipGetErrorString(rc); for (Job& j : jobs) j.out_len = 0; return -1; }
-    if (e8) {
-      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { for (Job& j : jobs) j.out_len = 0; return -1; }
-      for (size_t k = 0; k < fb.size(); ++k) if (fst[k] != 0) { res[fwho[k]].status = kUnlzLong; jobs[fwho[k]].out_len = 0; }
-    }
-    for (size_t i = 0; i < n; ++i) {
-      if (res[i].status != kUnlzOk) continue;
-      if (jobs[i].vec) jobs[i].vec->resize(res[i].out_len);
-      uint8_t* dst = jobs[i].vec ? jobs[i].vec->data() : jobs[i].out;
-      if (res[i].out_len) HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + off[i], res[i].out_len, hipMemcpyDeviceToHost, e.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-  }
-  for (size_t i = 0; i < n; ++i) if (res[i].status == kUnlzOk) jobs[i].status = 0;
-  return 1;
-}
-int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note) {
-  return lz77_decode_batch(level, rb, min_match, mbits, jobs, note, false);
-}
-
-// device/bwt_decode_kernel.h for a batch of host streams.  The host admits the streams (the rule, the range), so every size is
-// known and the room is checked before anything runs; then one upload, the six kernels, a word per stream back, and the outputs
-// of the streams whose path was whole down.  e8: as for lz77_decode_batch.
-template <class Job>
-static int bwt_decode_batch(U32 mbits, std::vector<Job>& jobs, std::string& note, bool e8) {
-  const size_t n = jobs.size();
-  if (!n) return 1;
-  for (Job& j : jobs) { j.status = 1; j.out_len = 0; }
-  if (n > 65535 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
-  std::vector<BwtStream> st;
-  std::vector<size_t> who;                          // st[k] is jobs[who[k]]
-  std::vector<char> empty(n, 0);
-  uint64_t in_bytes = 0, nodes = 0, tiles = 0, splits = 0, room = 0;
-  bool fits = true;
-  for (size_t i = 0; i < n; ++i) {
-    const Job& j = jobs[i];
-    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
-    BwtStream S;
-    memset(&S, 0, sizeof(S));
-    if (!bwt_stream_admitted(j.in, j.in_len, mbits, S.n, S.idx)) continue;
-    S.in_off = in_bytes;
-    S.link_off = nodes;
-    S.out_off = room;
-    S.tile_off = (uint32_t)tiles;
-    S.sp_off = (uint32_t)splits;
-    in_bytes += ((uint64_t)j.in_len + 3) & ~3ull;
-    nodes += (uint64_t)S.n + 1;
-    tiles += bwt_tiles(S.n);
-    splits += bwt_splitters(S.n);
-    room += e8 ? e8_room(S.n) : S.n;
-    jobs[i].out_len = S.n;
-    if (!j.vec && S.n > j.cap) fits = false;
-    st.push_back(S);
-    who.push_back(i);
-  }
-  const size_t m = st.size();
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Job& j : jobs) j.out_len = 0; return -1; }
-  if (!fits) return 0;
-  if (m) {
-    Engine& e = eng();
-    std::lock_guard<std::mutex> g(e.mu);
-    require_ready(e);
-    bind_device(e);
-    wait_in_flight(e);
-    // the arena buffer (idle between batches): the list, the tile histograms, the splitters, the stream table, the statuses
-    const uint64_t o_hist = (4 * nodes + 255) & ~255ull;
-    const uint64_t o_sp = (o_hist + 1024 * tiles + 255) & ~255ull;
-    const uint64_t o_st = (o_sp + 16 * splits + 255) & ~255ull;
-    const uint64_t o_res = (o_st + m * sizeof(BwtStream) + 255) & ~255ull;
-    const uint64_t ws = o_res + 4 * m + 256;
-    uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
-    for (size_t k = 0; k < m && e8; ++k) f_tiles += e8_tiles(st[k].n);
-    const uint64_t f_off = e8 ? (room + 255) & ~255ull : room, f_ws = e8 ? une8_ws(m, f_tiles).bytes : 0;
-    if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; for (Job& j : jobs) j.out_len = 0; return -1; }
-    e.io_in.ensure(in_bytes + 64);
-    e.io_out.ensure(f_off + f_ws + 64);
-    e.arena.ensure(ws);
-    uint8_t* const ab = (uint8_t*)e.arena.p;
-    std::unique_ptr<uint8_t[]> stage(new uint8_t[in_bytes + 64]);
-    for (size_t k = 0; k < m; ++k) {
-      const Job& j = jobs[who[k]];
-      uint8_t* at = stage.get() + st[k].in_off;
-      memcpy(at, j.in, j.in_len);
-      memset(at + j.in_len, 0, (size_t)((0u - j.in_len) & 3u));
-    }
-    HIP_CHECK(hipMemcpyAsync(e.io_in.p, stage.get(), in_bytes, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
-    const hipError_t rc = launch_bwt_decode((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (uint32_t)m, (uint32_t)tiles, (uint32_t)splits,
-                                            (uint32_t*)(ab + o_hist), (uint32_t*)ab, ab + o_sp, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device BWT decoder failed: ") + hipGetErrorString(rc); for (Job& j : jobs) j.out_len = 0; return -1; }
-    std::vector<uint32_t> res(m);
-    HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    if (e8) {
-      std::vector<E8Block> fb;
-      std::vector<size_t> fk;
-      std::vector<uint32_t> fst;
-      uint64_t tiles = 0;
-      for (size_t k = 0; k < m; ++k) {
-        if (res[k] != 0) continue;
-        fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
-        fk.push_back(k);
-        tiles += e8_tiles(st[k].n);
-      }
-      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { for (Job& j : jobs) j.out_len = 0; return -1; }
-      for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
-    }
-    for (size_t k = 0; k < m; ++k) {
-      Job& j = jobs[who[k]];
-      if (res[k] != 0) { j.out_len = 0; continue; }
-      if (j.vec) j.vec->resize(st[k].n);
-      uint8_t* dst = j.vec ? j.vec->data() : j.out;
-      HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + st[k].out_off, st[k].n, hipMemcpyDeviceToHost, e.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
-  }
-  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
-  return 1;
-}
-int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note) { return bwt_decode_batch(mbits, jobs, note, false); }
-
-// Streams of the E8E9 methods back into their blocks: the stage in front with the method's own parameters (kind 5 / 6: the LZ77
-// decoder, kind 7: the BWT decoder, kind 4: none -- the stream is the filtered block), then device/e8e9_kernel.h over its output
-// while that is still on the device.
-int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<Une8Job>& jobs, std::string& note) {
-  if (kind == 5 || kind == 6) return lz77_decode_batch((U32)(kind - 4), rb, min_match, mbits, jobs, note, true);
-  if (kind == 7) return bwt_decode_batch(mbits, jobs, note, true);
-  const size_t n = jobs.size();
-  if (!n) return 1;
-  for (Une8Job& j : jobs) { j.status = 1; j.out_len = 0; }
-  if (n > 65535 || kind != 4) { note = "batch outside the device filter's range"; return -1; }
-  std::vector<E8Block> fb(n);
-  uint64_t room = 0, tiles = 0;
-  bool fits = true;
-  for (size_t i = 0; i < n; ++i) {
-    fb[i] = E8Block{room, jobs[i].in_len, (uint32_t)tiles};
-    room += e8_room(jobs[i].in_len);
-    tiles += e8_tiles(jobs[i].in_len);
-    jobs[i].out_len = jobs[i].in_len;
-    if (!jobs[i].vec && jobs[i].in_len > jobs[i].cap) fits = false;
-  }
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; for (Une8Job& j : jobs) j.out_len = 0; return -1; }
-  if (!fits) return 0;
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  const uint64_t f_off = (room + 255) & ~255ull, f_ws = une8_ws(n, tiles).bytes;
-  if (f_off + f_ws + (1u << 20) > e.budget) { note = "the blocks exceed the device budget"; for (Une8Job& j : jobs) j.out_len = 0; return -1; }
-  e.io_out.ensure(f_off + f_ws + 64);
-  if (room) {
-    std::unique_ptr<uint8_t[]> stage(new uint8_t[room]);
-    for (size_t i = 0; i < n; ++i) {
-      uint8_t* at = stage.get() + fb[i].off;
-      if (jobs[i].in_len) memcpy(at, jobs[i].in, jobs[i].in_len);
-      memset(at + jobs[i].in_len, 0, (size_t)(e8_room(jobs[i].in_len) - jobs[i].in_len));
-    }
-    HIP_CHECK(hipMemcpyAsync(e.io_out.p, stage.get(), room, hipMemcpyHostToDevice, e.stream));
-  }
-  std::vector<uint32_t> fst;
-  if (!une8_run(e, f_off, fb, tiles, f_off + f_ws, fst, note)) { for (Une8Job& j : jobs) j.out_len = 0; return -1; }
-  for (size_t i = 0; i < n; ++i) {
-    Une8Job& j = jobs[i];
-    if (fst[i] != 0) { j.out_len = 0; continue; }
-    if (j.vec) j.vec->resize(j.in_len);
-    uint8_t* dst = j.vec ? j.vec->data() : j.out;
-    if (j.in_len) HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + fb[i].off, j.in_len, hipMemcpyDeviceToHost, e.stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  for (size_t i = 0; i < n; ++i) if (fst[i] == 0) jobs[i].status = 0;
-  return 1;
-}
-
-// device/fragment_kernel.h for a batch of host files: one upload, round 0 (every piece from its own start), the stitch rounds
-// (engine.hpp), one SHA-1 job per final fragment.  The records of a launch come back in runs of neighbouring lists.
-namespace {
-std::atomic<U32> g_last_fragment_rounds{0};
-}
-U32 engine_last_fragment_rounds() { return g_last_fragment_rounds.load(std::memory_order_relaxed); }
-
-int engine_fragment(const U8* const* in, const U64* len, U32 n, const FragLimits& lim, std::vector<std::vector<Fragment>>& out, std::string& note) {
-  out.assign(n, std::vector<Fragment>());
-  g_last_fragment_rounds.store(0, std::memory_order_relaxed);
-  if (!n) return 1;
-  U64 piece = std::max<U64>(kFragPiece, 64ull * lim.min_frag);    // (walks re-join after a few fragments: keep that a fraction of a piece)
-  if (const char* v = getenv("ZPAQ_AMD_FRAG_PIECE")) { const long long x = atoll(v); if (x > 0) piece = (U64)x; }
-  piece = std::min<U64>(std::max<U64>(piece, 64), 1u << 30);
-  if (n > 65535) { note = "more than 65 535 files in one batch"; return -1; }
-  if (!lim.min_frag || lim.max_frag < lim.min_frag) { note = "fragment limits out of range"; return -1; }
-  std::vector<U64> off(n);
-  U64 bytes = 0;
-  for (U32 f = 0; f < n; ++f) {
-    off[f] = bytes;
-    if (len[f] > (1ull << 31)) { note = "more than 2 GiB of input in one batch"; return -1; }
-    bytes += (len[f] + 63) & ~63ull;
-  }
-  if (bytes > (1ull << 31)) { note = "more than 2 GiB of input in one batch"; return -1; }
-  FragPlan pl;
-  if (!frag_plan(len, n, piece, lim.min_frag, pl)) { note = "the record lists exceed the device budget"; return -1; }
-  const size_t m = pl.pc.size();
-  const U64 nrec = pl.nrec;
-  const bool pieces = pl.pieces;                    // fix-ups write into a second set of lists
-  const U64 rec_bytes = nrec * sizeof(FragRec) * (pieces ? 2u : 1u);
-  Engine& e = eng();
-  std::lock_guard<std::mutex> g(e.mu);
-  require_ready(e);
-  bind_device(e);
-  wait_in_flight(e);
-  if (bytes + rec_bytes + m * (sizeof(FragJob) + sizeof(FragResult)) + (1u << 20) > e.budget) { note = "the files and the record lists exceed the device budget"; return -1; }
-  e.io_in.ensure(bytes + 64);
-  e.io_out.ensure(rec_bytes + 64);
-  e.jobs.ensure(m * sizeof(FragJob));
-  e.results.ensure(m * sizeof(FragResult));
-  uint8_t* const ib = (uint8_t*)e.io_in.p;
-  FragRec* const recs = (FragRec*)e.io_out.p;
-  // the upload: a large file goes as it lies, runs of small ones through one staging buffer
-  const U64 kDirect = 1u << 20;
-  U64 small = 0;
-  for (U32 f = 0; f < n; ++f) if (len[f] < kDirect) small += (len[f] + 63) & ~63ull;
-  std::unique_ptr<uint8_t[]> stage(new uint8_t[small + 64]);
-  U64 at = 0;
-  for (U32 f = 0; f < n;) {
-    if (len[f] >= kDirect) { HIP_CHECK(hipMemcpyAsync(ib + off[f], in[f], len[f], hipMemcpyHostToDevice, e.stream)); ++f; continue; }
-    const U32 f0 = f;
-    const U64 at0 = at;
-    for (; f < n && len[f] < kDirect; ++f) {
-      if (len[f]) memcpy(stage.get() + at, in[f], len[f]);
-      at += (len[f] + 63) & ~63ull;
-    }
-    if (at > at0) HIP_CHECK(hipMemcpyAsync(ib + off[f0], stage.get() + at0, at - at0, hipMemcpyHostToDevice, e.stream));
-  }
-  FragParams P;
-  P.min_frag = lim.min_frag; P.max_frag = lim.max_frag; P.thresh = lim.thresh;
-  // one launch: the jobs up, the walk, how each ended and its records down (the jobs' lists ascend in the record array)
-  auto run = [&](const std::vector<FragJob>& jb, std::vector<FragResult>& rs, std::vector<std::vector<FragRec>>& lists) -> bool {
-    const size_t q = jb.size();
-    rs.resize(q);
-    lists.assign(q, std::vector<FragRec>());
-    HIP_CHECK(hipMemcpyAsync(e.jobs.p, jb.data(), q * sizeof(FragJob), hipMemcpyHostToDevice, e.stream));
-    const hipError_t rc = launch_frag_walk(ib, (const FragJob*)e.jobs.p, (uint32_t)q, P, recs, (FragResult*)e.results.p, e.stream);
-    if (rc != hipSuccess) { (void)hipGetLastError(); note = std::string("device fragment walk failed: ") + hipGetErrorString(rc); return false; }
-    HIP_CHECK(hipMemcpyAsync(rs.data(), e.results.p, q * sizeof(FragResult), hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    if (!frag_results_ok(jb, rs)) { note = "device fragment walk: a record list overflowed"; return false; }
-    std::vector<FragRec> tmp;
-    for (size_t i = 0; i < q;) {
-      size_t j = i;
-      const U64 a = jb[i].rec_off;
-      U64 b = a + rs[i].count;
-      while (j + 1 < q && jb[j + 1].rec_off - b <= 256u && jb[j + 1].rec_off + rs[j + 1].count - a <= (1u << 16)) { ++j; b = (U64)jb[j].rec_off + rs[j].count; }
-      tmp.resize((size_t)(b - a));
-      HIP_CHECK(hipMemcpyAsync(tmp.data(), recs + a, (size_t)(b - a) * sizeof(FragRec), hipMemcpyDeviceToHost, e.stream));
-      HIP_CHECK(hipStreamSynchronize(e.stream));
-      for (size_t k = i; k <= j; ++k) lists[k].assign(tmp.begin() + (jb[k].rec_off - a), tmp.begin() + (jb[k].rec_off - a) + rs[k].count);
-      i = j + 1;
-    }
-    return true;
-  };
-  std::vector<std::vector<FragRec>> fin;
-  U32 rounds = 0;
-  if (!frag_stitch(pl, off.data(), len, n, piece, run, fin, rounds, note)) return -1;
-  // one SHA-1 job per fragment
-  U64 total = 0;
-  for (U32 f = 0; f < n; ++f) total += fin[f].size();
-  if (total >= (1ull << 31)) { note = "too many fragments"; return -1; }
-  std::vector<Sha1Job> sj((size_t)total);
-  size_t s = 0;
-  for (U32 f = 0; f < n; ++f) {
-    uint32_t from = 0;
-    out[f].resize(fin[f].size());
-    for (size_t k = 0; k < fin[f].size(); ++k) {
-      const FragRec& r = fin[f][k];
-      Fragment& o = out[f][k];
-      o.size = r.end - from;
-      o.hits = r.hits;
-      memcpy(o.o1, r.o1, 256);
-      sj[s] = Sha1Job{ib + off[f] + from, o.size, (uint32_t)s};
-      ++s;
-      from = r.end;
-    }
-  }
-  e.sha_jobs.ensure((size_t)total * sizeof(Sha1Job));
-  e.sha_out.ensure((size_t)total * 20);
-  std::vector<uint8_t> dig((size_t)total * 20);
-  HIP_CHECK(hipMemcpyAsync(e.sha_jobs.p, sj.data(), (size_t)total * sizeof(Sha1Job), hipMemcpyHostToDevice, e.stream));
-  HIP_CHECK(launch_sha1((const Sha1Job*)e.sha_jobs.p, (uint32_t)total, (uint8_t*)e.sha_out.p, e.stream));
-  HIP_CHECK(hipMemcpyAsync(dig.data(), e.sha_out.p, (size_t)total * 20, hipMemcpyDeviceToHost, e.stream));
-  HIP_CHECK(hipStreamSynchronize(e.stream));
-  s = 0;
-  for (U32 f = 0; f < n; ++f) for (Fragment& o : out[f]) { memcpy(o.sha1, dig.data() + 20 * s, 20); ++s; }
-  g_last_fragment_rounds.store(rounds, std::memory_order_relaxed);
-  return 1;
-}
 
 int engine_jit_threads() { return jit_threads(); }
 

@@ -120,13 +120,16 @@ inline bool hash_job_in_range(const SortJob& j) {
 // -1 + note: the device declines (blocks of 2^24 bytes and more, more than 65 535 blocks, 2 GiB per batch, memory).
 struct CodeJob { const U8* data; U32 n, kind, min_match, rb; const LzToken* toks; size_t ntok; };
 int engine_lz77_codes(const std::vector<CodeJob>& jobs, std::vector<std::vector<U8>>& out, std::string& note);
+// One stream of a batch the device decodes back into its block (engine_lz77_decode, engine_bwt_decode, engine_e8e9_decode): the
+// output goes to `vec` (resized) when set, else to out[0..cap).  status 0: decoded, out_len bytes; 1: declined, the output untouched --
+// the device never gives a verdict on a stream, the caller's other route does.  The three calls return 1: done, status / out_len
+// per job; 0: some decoded block does not fit its cap -- every out_len is reported, nothing is written; -1 + note: the device
+// declines the batch.
+struct StreamJob { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
 // LZ77 streams of one method back into their blocks on the device (device/lz77_decode_kernel.h): what the method's PCOMP program
-// (level 1 / 2 without E8E9; rb = lz_offset_rb, mbits = the program's pm) makes of each stream, or status 1: declined, the output
-// untouched -- the device never gives a verdict on a stream.  The output goes to `vec` (resized) when set, else to out[0..cap).
-// 1: done, status / out_len per job; 0: some decoded block does not fit its cap -- every out_len is reported, nothing is written;
-// -1 + note: the device declines the batch (more than 65 535 streams, 2 GiB of output, memory).
-struct UnlzJob { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
-int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<UnlzJob>& jobs, std::string& note);
+// (level 1 / 2 without E8E9; rb = lz_offset_rb, mbits = the program's pm) makes of each stream.  The batch is declined
+// (-1 + note) beyond 65 535 streams, 2 GiB of output, or the engine's budget.
+int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note);
 // Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNLZ is unset: from the smallest batch at which
 // it was faster than both other routes (the translated program on the device, a lane per segment; the host's translated
 // programs) in every alternation of the measurement -- 256 segments of 1 MiB (DESIGN 4.5.3 has the table and the rule).
@@ -138,8 +141,7 @@ inline bool lz_unlz_pays(U64 segments, U64 /*stream_bytes*/) { return segments >
 // 1: done, status / out_len per job; 0: some admitted stream does not fit its cap -- every out_len is reported, nothing is
 // launched or written; -1 + note: the device declines the batch (more than 65 535 streams, 2 GiB of output, memory: 4 bytes per
 // stream byte, the tile histograms, the splitter tables and the outputs count against the engine's budget).
-struct UnbwtJob { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
-int engine_bwt_decode(U32 mbits, std::vector<UnbwtJob>& jobs, std::string& note);
+int engine_bwt_decode(U32 mbits, std::vector<StreamJob>& jobs, std::string& note);
 // Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNBWT is unset.  The rule is the one of
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
@@ -149,11 +151,10 @@ inline bool bwt_unbwt_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return fals
 // filter over the stage's output while it is on the device (device/e8e9_kernel.h: candidates, seeds and breaks marked from the
 // original bytes, a lane per chain's first seed walks it), then the blocks down.  What the method's program makes of each stream,
 // or status 1: declined, the output untouched -- whatever the stage in front declines (an output beyond 2^mbits among it: the
-// programs filter M, which wraps there), and a block in which a lane gave up after kE8MaxSteps serial steps.  1 / 0 / -1 as for
-// engine_lz77_decode (kinds 4 and 7 know every size before anything runs); 65 535 streams and 2 GiB of output per batch; the
+// programs filter M, which wraps there), and a block in which a lane gave up after kE8MaxSteps serial steps.  1 / 0 / -1 as
+// StreamJob says (kinds 4 and 7 know every size before anything runs); 65 535 streams and 2 GiB of output per batch; the
 // tiles' counts and the list of seeds and breaks (4 bytes each) count against the engine's budget.
-struct Une8Job { const U8* in; U32 in_len; U8* out; U64 cap; std::vector<U8>* vec; U64 out_len = 0; int status = 1; };
-int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<Une8Job>& jobs, std::string& note);
+int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note);
 // Whether a group of qualifying segments takes that route when ZPAQ_AMD_DEVICE_UNE8 is unset.  The rule is the one of
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.

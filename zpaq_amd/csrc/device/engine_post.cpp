@@ -1,0 +1,373 @@
+// The engine's batch stages of the decompression side: the archive's own PCOMP program a lane per segment, and the decoders of the
+// standard methods' streams -- LZ77, BWT, and either (or nothing) behind the inverse E8E9 filter.  Each takes the engine for one
+// call (EngineCall), sums what its batch holds on the device against the engine's budget, stages its inputs, launches, and
+// delivers or declines.
+#include <algorithm>
+
+#include "engine_internal.hpp"
+#include "kernels.h"
+#include "sa_kernels.h"
+#include "spec_loader.hpp"
+
+namespace zpq {
+
+bool engine_pcomp(const U8* code, size_t codelen, int ph, int pm, std::vector<PcompSeg>& segs, std::string& note, bool* handed_back) {
+  if (handed_back) *handed_back = false;
+  if (segs.empty()) return true;
+  EngineCall call;
+  Engine& e = call.e;
+  PcompKernel* k = pcomp_kernel_for(code, codelen, ph, pm, note);
+  if (!k) return false;
+  if (handed_back) *handed_back = true;          // (every false from here on)
+  const size_t n = segs.size();
+  const uint64_t mbytes = align_up(1ull << pm, 256), hbytes = align_up(4ull << ph, 256);
+  std::vector<uint64_t> cap(n);
+  for (size_t i = 0; i < n; ++i) cap[i] = (segs[i].hint ? segs[i].hint : 8ull * segs[i].in_len) + 65536;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    uint64_t in_bytes = 0, out_bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (cap[i] > 0xFFFFFFF0ull) { note = "segment output beyond the device kernel's 32-bit range"; return false; }   // the host runs it (the size hint is a comment the reference ignores)
+      in_bytes += align_up(segs[i].in_len, 64);
+      out_bytes += align_up(cap[i], 64);
+    }
+    const uint64_t work = (uint64_t)n * (mbytes + hbytes + 1024);
+    if (in_bytes + out_bytes + work > e.budget) { note = "post-processor state exceeds the device budget"; return false; }
+    e.io_in.ensure(in_bytes + 64);
+    e.io_out.ensure(out_bytes + 64);
+    e.arena.ensure(work);
+    e.jobs.ensure(n * sizeof(PcompJob));
+    e.results.ensure(n * 8);
+    std::vector<HostItem> items(n);
+    std::vector<PcompJob> jobs(n);
+    std::vector<uint64_t> ooff(n);
+    uint64_t io = 0, oo = 0;
+    for (size_t i = 0; i < n; ++i) {
+      items[i] = HostItem{segs[i].in, segs[i].in_len, io};
+      PcompJob& j = jobs[i];
+      j.in = (const uint8_t*)e.io_in.p + io;
+      j.out = (uint8_t*)e.io_out.p + oo;
+      uint8_t* w = (uint8_t*)e.arena.p + (uint64_t)i * (mbytes + hbytes + 1024);
+      j.M = w;
+      j.H = (uint32_t*)(w + mbytes);
+      j.R = (uint32_t*)(w + mbytes + hbytes);
+      j.in_len = segs[i].in_len;
+      j.out_cap = (uint32_t)cap[i];
+      j.result = (uint32_t*)e.results.p + 2 * i;
+      ooff[i] = oo;
+      io += align_up(segs[i].in_len, 64);
+      oo += align_up(cap[i], 64);
+    }
+    HIP_CHECK(hipMemsetAsync(e.arena.p, 0, work, e.stream));
+    const auto staged = upload_staged(e, e.io_in.p, items, in_bytes, 64, false);
+    HIP_CHECK(hipMemcpyAsync(e.jobs.p, jobs.data(), n * sizeof(PcompJob), hipMemcpyHostToDevice, e.stream));
+    const PcompJob* d_jobs = (const PcompJob*)e.jobs.p;
+    unsigned nn = (unsigned)n;
+    void* args[2] = {(void*)&d_jobs, (void*)&nn};
+    HIP_CHECK(hipModuleLaunchKernel(k->fn, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, e.stream, args, nullptr));
+    std::vector<uint32_t> res(2 * n);
+    HIP_CHECK(hipMemcpyAsync(res.data(), e.results.p, n * 8, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    bool again = false;
+    for (size_t i = 0; i < n; ++i) {
+      // a device status is not a verdict: the translated program has a fixed budget of backward jumps, so the host
+      // post-processor (which owns the ZPAQL-error decision, like the reference's) runs these segments again
+      if (res[2 * i + 1]) { note = "device post-processor stopped (status " + std::to_string(res[2 * i + 1]) + "): host fallback"; return false; }
+      if (res[2 * i] > cap[i]) { cap[i] = res[2 * i]; again = true; }
+    }
+    if (again && attempt == 0) continue;
+    for (size_t i = 0; i < n; ++i) {
+      segs[i].out->resize(res[2 * i]);
+      if (res[2 * i])
+        HIP_CHECK(hipMemcpyAsync(segs[i].out->data(), (const uint8_t*)e.io_out.p + ooff[i], res[2 * i], hipMemcpyDeviceToHost, e.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    return true;
+  }
+  return false;
+}
+
+// The download of a decoded block (`len` bytes at `off` of io_out): into the job's vector, resized, when it has one, else into
+// its buffer
+static void deliver(Engine& e, StreamJob& j, uint64_t off, uint64_t len) {
+  if (j.vec) j.vec->resize(len);
+  uint8_t* dst = j.vec ? j.vec->data() : j.out;
+  if (len) HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)e.io_out.p + off, len, hipMemcpyDeviceToHost, e.stream));
+}
+// the device declines the batch behind the point where sizes were reported: none stays (-1 + note)
+static int declined(std::vector<StreamJob>& jobs) {
+  for (StreamJob& j : jobs) j.out_len = 0;
+  return -1;
+}
+
+// device/e8e9_kernel.h over blocks that lie in io_out, in place.  The caller placed them (offsets multiples of 16, the rooms rounded
+// up) and ensured une8_ws(..).bytes of io_out at ws_off (a multiple of 256) for the first half: the block table, the tiles' counts,
+// the statuses, the scan's scratch.  The list of seeds and breaks is sized from the two totals the host reads between the halves
+// and goes to io_in, whose content the caller needs no longer; `held` = what the batch holds besides it.  status[k] = 0: block k
+// is filtered; 1: a lane gave it up, its bytes are to be dropped.  false + note: nothing is to be delivered.
+struct E8Ws { uint64_t o_cnt, o_st, o_tmp, bytes; size_t tmp_bytes; };
+static E8Ws une8_ws(size_t m, uint64_t ntiles) {
+  E8Ws w;
+  Carve cv;
+  cv.take(m * sizeof(E8Block));
+  w.o_cnt = cv.take(4 * (2 * ntiles + 1));
+  w.o_st = cv.take(4 * m);
+  w.tmp_bytes = une8_scan_bytes((uint32_t)ntiles);
+  w.o_tmp = cv.take(w.tmp_bytes);
+  w.bytes = cv.at + 256;
+  return w;
+}
+static bool une8_run(Engine& e, uint64_t ws_off, const std::vector<E8Block>& blk, uint64_t ntiles, uint64_t held, std::vector<uint32_t>& status,
+                     std::string& note) {
+  const size_t m = blk.size();
+  status.assign(m, 1u);
+  if (!m) return true;
+  const E8Ws w = une8_ws(m, ntiles);
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  uint8_t* const wb = ob + ws_off;
+  uint32_t* const cnt = (uint32_t*)(wb + w.o_cnt);
+  HIP_CHECK(hipMemcpyAsync(wb, blk.data(), m * sizeof(E8Block), hipMemcpyHostToDevice, e.stream));
+  hipError_t rc = launch_une8_mark(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)(wb + w.o_st), wb + w.o_tmp, w.tmp_bytes, e.stream);
+  if (launch_failed(rc, "device E8E9 filter failed: ", note)) return false;
+  uint32_t nseeds = 0, nlist = 0;
+  HIP_CHECK(hipMemcpyAsync(&nseeds, cnt + ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipMemcpyAsync(&nlist, cnt + 2 * ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (nseeds) {
+    if (held + 4ull * nlist + (1u << 20) > e.budget) { note = "the filter's list exceeds the device budget"; return false; }
+    e.io_in.ensure(4ull * nlist + 64);
+    rc = launch_une8_walk(ob, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)e.io_in.p, nseeds, kE8MaxSteps, (uint32_t*)(wb + w.o_st), e.stream);
+    if (launch_failed(rc, "device E8E9 filter failed: ", note)) return false;
+  }
+  HIP_CHECK(hipMemcpyAsync(status.data(), wb + w.o_st, 4 * m, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  return true;
+}
+
+// device/lz77_decode_kernel.h for a batch of host streams: one upload, the parse, 12 bytes per stream back, the outputs placed
+// back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.  e8: the method's program filters
+// M before it writes it out -- the outputs are placed for device/e8e9_kernel.h, which runs over them before they go down.
+static int lz77_decode_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
+  std::vector<UnlzStream> st(n);
+  uint64_t in_bytes = 0, ntok = 0;
+  for (size_t i = 0; i < n; ++i) {
+    UnlzStream& S = st[i];
+    memset(&S, 0, sizeof(S));
+    S.in_off = in_bytes;
+    S.tok_off = ntok;
+    S.in_len = jobs[i].in_len;
+    S.tok_cap = jobs[i].in_len;                      // a code has at least 8 bits: at most one token per stream byte
+    S.level = level;
+    S.rb = rb;
+    S.min_match = min_match;
+    S.mbits = mbits;
+    in_bytes += align_up(jobs[i].in_len, 4);
+    ntok += jobs[i].in_len;
+  }
+  EngineCall call;
+  Engine& e = call.e;
+  // the arena buffer (idle between batches): tokens, the stream table, the results, where the outputs start
+  Carve cv;
+  cv.take(16 * ntok);
+  const uint64_t o_st = cv.take(n * sizeof(UnlzStream));
+  const uint64_t o_res = cv.take(n * sizeof(UnlzResult));
+  const uint64_t o_off = cv.take(8 * n);
+  const uint64_t ws = cv.at + 256;
+  if (ws + in_bytes + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return -1; }
+  e.io_in.ensure(in_bytes + 64);
+  e.arena.ensure(ws);
+  uint8_t* const ab = (uint8_t*)e.arena.p;
+  std::vector<HostItem> items(n);
+  for (size_t i = 0; i < n; ++i) items[i] = HostItem{jobs[i].in, jobs[i].in_len, st[i].in_off};
+  const auto staged = upload_staged(e, e.io_in.p, items, in_bytes, 4, false);
+  HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), n * sizeof(UnlzStream), hipMemcpyHostToDevice, e.stream));
+  hipError_t rc = launch_unlz_parse((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (UnlzResult*)(ab + o_res), e.stream);
+  if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return -1;
+  std::vector<UnlzResult> res(n);
+  HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, n * sizeof(UnlzResult), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  std::vector<uint64_t> off(n);
+  uint64_t room = 0, tiles = 0;
+  bool fits = true, any = false;
+  std::vector<E8Block> fb;                          // e8: the decoded blocks as the filter sees them, fb[k] is jobs[fwho[k]]
+  std::vector<size_t> fwho;
+  for (size_t i = 0; i < n; ++i) {
+    off[i] = room;
+    if (res[i].status != kUnlzOk) continue;
+    jobs[i].out_len = res[i].out_len;
+    if (e8) {
+      fb.push_back(E8Block{room, res[i].out_len, (uint32_t)tiles});
+      fwho.push_back(i);
+      tiles += e8_tiles(res[i].out_len);
+    }
+    room += e8 ? e8_room(res[i].out_len) : res[i].out_len;
+    any = true;
+    if (!jobs[i].vec && res[i].out_len > jobs[i].cap) fits = false;
+  }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
+  const uint64_t f_off = e8 ? align_up(room, 256) : room, f_ws = e8 ? une8_ws(fb.size(), tiles).bytes : 0;
+  if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; return declined(jobs); }
+  if (!fits) return 0;
+  std::vector<uint32_t> fst;
+  if (any) {
+    e.io_out.ensure(f_off + f_ws + 64);
+    HIP_CHECK(hipMemcpyAsync(ab + o_off, off.data(), 8 * n, hipMemcpyHostToDevice, e.stream));
+    rc = launch_unlz_copy((const uint8_t*)e.io_in.p, (const UnlzStream*)(ab + o_st), (uint32_t)n, ab, (const UnlzResult*)(ab + o_res),
+                          (const uint64_t*)(ab + o_off), (uint8_t*)e.io_out.p, e.stream);
+    if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return declined(jobs);
+    if (e8) {
+      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) return declined(jobs);
+      for (size_t k = 0; k < fb.size(); ++k) if (fst[k] != 0) { res[fwho[k]].status = kUnlzLong; jobs[fwho[k]].out_len = 0; }
+    }
+    for (size_t i = 0; i < n; ++i) {
+      if (res[i].status != kUnlzOk) continue;
+      deliver(e, jobs[i], off[i], res[i].out_len);
+    }
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+  }
+  for (size_t i = 0; i < n; ++i) if (res[i].status == kUnlzOk) jobs[i].status = 0;
+  return 1;
+}
+int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+  return lz77_decode_batch(level, rb, min_match, mbits, jobs, note, false);
+}
+
+// device/bwt_decode_kernel.h for a batch of host streams.  The host admits the streams (the rule, the range), so every size is
+// known and the room is checked before anything runs; then one upload, the six kernels, a word per stream back, and the outputs
+// of the streams whose path was whole down.  e8: as for lz77_decode_batch.
+static int bwt_decode_batch(U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
+  std::vector<BwtStream> st;
+  std::vector<size_t> who;                          // st[k] is jobs[who[k]]
+  std::vector<char> empty(n, 0);
+  uint64_t in_bytes = 0, nodes = 0, tiles = 0, splits = 0, room = 0;
+  bool fits = true;
+  for (size_t i = 0; i < n; ++i) {
+    const StreamJob& j = jobs[i];
+    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
+    BwtStream S;
+    memset(&S, 0, sizeof(S));
+    if (!bwt_stream_admitted(j.in, j.in_len, mbits, S.n, S.idx)) continue;
+    S.in_off = in_bytes;
+    S.link_off = nodes;
+    S.out_off = room;
+    S.tile_off = (uint32_t)tiles;
+    S.sp_off = (uint32_t)splits;
+    in_bytes += align_up(j.in_len, 4);
+    nodes += (uint64_t)S.n + 1;
+    tiles += bwt_tiles(S.n);
+    splits += bwt_splitters(S.n);
+    room += e8 ? e8_room(S.n) : S.n;
+    jobs[i].out_len = S.n;
+    if (!j.vec && S.n > j.cap) fits = false;
+    st.push_back(S);
+    who.push_back(i);
+  }
+  const size_t m = st.size();
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
+  if (!fits) return 0;
+  if (m) {
+    EngineCall call;
+    Engine& e = call.e;
+    // the arena buffer (idle between batches): the list, the tile histograms, the splitters, the stream table, the statuses
+    Carve cv;
+    cv.take(4 * nodes);
+    const uint64_t o_hist = cv.take(1024 * tiles);
+    const uint64_t o_sp = cv.take(16 * splits);
+    const uint64_t o_st = cv.take(m * sizeof(BwtStream));
+    const uint64_t o_res = cv.take(4 * m);
+    const uint64_t ws = cv.at + 256;
+    uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
+    for (size_t k = 0; k < m && e8; ++k) f_tiles += e8_tiles(st[k].n);
+    const uint64_t f_off = e8 ? align_up(room, 256) : room, f_ws = e8 ? une8_ws(m, f_tiles).bytes : 0;
+    if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return declined(jobs); }
+    e.io_in.ensure(in_bytes + 64);
+    e.io_out.ensure(f_off + f_ws + 64);
+    e.arena.ensure(ws);
+    uint8_t* const ab = (uint8_t*)e.arena.p;
+    std::vector<HostItem> items(m);
+    for (size_t k = 0; k < m; ++k) items[k] = HostItem{jobs[who[k]].in, jobs[who[k]].in_len, st[k].in_off};
+    const auto staged = upload_staged(e, e.io_in.p, items, in_bytes, 4, false);
+    HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
+    const hipError_t rc = launch_bwt_decode((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (uint32_t)m, (uint32_t)tiles, (uint32_t)splits,
+                                            (uint32_t*)(ab + o_hist), (uint32_t*)ab, ab + o_sp, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
+    if (launch_failed(rc, "device BWT decoder failed: ", note)) return declined(jobs);
+    std::vector<uint32_t> res(m);
+    HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    if (e8) {
+      std::vector<E8Block> fb;
+      std::vector<size_t> fk;
+      std::vector<uint32_t> fst;
+      uint64_t tiles = 0;
+      for (size_t k = 0; k < m; ++k) {
+        if (res[k] != 0) continue;
+        fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
+        fk.push_back(k);
+        tiles += e8_tiles(st[k].n);
+      }
+      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) return declined(jobs);
+      for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
+    }
+    for (size_t k = 0; k < m; ++k) {
+      StreamJob& j = jobs[who[k]];
+      if (res[k] != 0) { j.out_len = 0; continue; }
+      deliver(e, j, st[k].out_off, st[k].n);
+    }
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
+  }
+  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
+  return 1;
+}
+int engine_bwt_decode(U32 mbits, std::vector<StreamJob>& jobs, std::string& note) { return bwt_decode_batch(mbits, jobs, note, false); }
+
+// Streams of the E8E9 methods back into their blocks: the stage in front with the method's own parameters (kind 5 / 6: the LZ77
+// decoder, kind 7: the BWT decoder, kind 4: none -- the stream is the filtered block), then device/e8e9_kernel.h over its output
+// while that is still on the device.
+int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+  if (kind == 5 || kind == 6) return lz77_decode_batch((U32)(kind - 4), rb, min_match, mbits, jobs, note, true);
+  if (kind == 7) return bwt_decode_batch(mbits, jobs, note, true);
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (n > 65535 || kind != 4) { note = "batch outside the device filter's range"; return -1; }
+  std::vector<E8Block> fb(n);
+  uint64_t room = 0, tiles = 0;
+  bool fits = true;
+  for (size_t i = 0; i < n; ++i) {
+    fb[i] = E8Block{room, jobs[i].in_len, (uint32_t)tiles};
+    room += e8_room(jobs[i].in_len);
+    tiles += e8_tiles(jobs[i].in_len);
+    jobs[i].out_len = jobs[i].in_len;
+    if (!jobs[i].vec && jobs[i].in_len > jobs[i].cap) fits = false;
+  }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
+  if (!fits) return 0;
+  EngineCall call;
+  Engine& e = call.e;
+  const uint64_t f_off = align_up(room, 256), f_ws = une8_ws(n, tiles).bytes;
+  if (f_off + f_ws + (1u << 20) > e.budget) { note = "the blocks exceed the device budget"; return declined(jobs); }
+  e.io_out.ensure(f_off + f_ws + 64);
+  std::vector<HostItem> items(n);
+  for (size_t i = 0; i < n; ++i) items[i] = HostItem{jobs[i].in, jobs[i].in_len, fb[i].off};
+  const auto staged = upload_staged(e, e.io_out.p, items, room, kE8Lane, false);      // (the rooms: e8_room rounds up to a lane's bytes)
+  std::vector<uint32_t> fst;
+  if (!une8_run(e, f_off, fb, tiles, f_off + f_ws, fst, note)) return declined(jobs);
+  for (size_t i = 0; i < n; ++i) {
+    StreamJob& j = jobs[i];
+    if (fst[i] != 0) { j.out_len = 0; continue; }
+    deliver(e, j, fb[i].off, j.in_len);
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t i = 0; i < n; ++i) if (fst[i] == 0) jobs[i].status = 0;
+  return 1;
+}
+
+}  // namespace zpq

@@ -26,8 +26,6 @@ const PipeLayout* plan_pipe_layout(const zpq_plan& plan, int variant, std::strin
 
 static const int kCompLen[10] = {0, 2, 3, 2, 3, 4, 6, 6, 3, 5};   // libzpaq.cpp:714
 
-static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
 // list_only: the caller only locates, lists or skips the block (Decompresser::findBlock): the header is checked with the
 // REFERENCE's limits (sizes up to 32, ZPAQL::read, libzpaq.cpp:887-1006) and only `memory` of the result means anything;
 // the limits of this build -- a block lane's tables live in HBM -- apply where a plan is needed to code or decode.

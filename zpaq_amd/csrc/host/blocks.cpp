@@ -529,7 +529,8 @@ std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
 // args[0] is pm - 20; level 2's minimum match is read where two generated programs differ, then confirmed by the whole comparison.
-struct UnlzProgram { U32 level, rb, min_match, mbits; };
+// kind: args[1] of the method -- 1 / 2 the LZ77 levels, 3 the BWT, 4 .. 7 the same (or nothing) behind E8E9.
+struct StreamProgram { int kind; U32 rb, min_match, mbits; };
 bool unlz_generated(int a0, const std::string& body, std::vector<U8>& key) {
   try {
     int args[9];
@@ -541,78 +542,66 @@ bool unlz_generated(int a0, const std::string& body, std::vector<U8>& key) {
     return true;
   } catch (const std::exception&) { return false; }
 }
-bool unlz_program(const std::vector<U8>& key, UnlzProgram& u) {
+bool unlz_program(const std::vector<U8>& key, StreamProgram& u) {
   if (key.size() < 3) return false;
   const int a0 = (int)key[1] - 20;
   if (key[0] != 0 || a0 < 0 || a0 > 11) return false;
   std::vector<U8> k1, k2;
-  if (unlz_generated(a0, ",1", k1) && k1 == key) { u = UnlzProgram{1u, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
+  if (unlz_generated(a0, ",1", k1) && k1 == key) { u = StreamProgram{1, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
   if (!unlz_generated(a0, ",2,1", k1) || !unlz_generated(a0, ",2,2", k2) || k1.size() != key.size() || k2.size() != key.size()) return false;
   size_t at = key.size(), differ = 0;
   for (size_t i = 0; i < key.size(); ++i) if (k1[i] != k2[i]) { at = i; ++differ; }
   if (differ != 1) return false;
   const U32 mm = key[at];
   if (!unlz_generated(a0, ",2," + std::to_string(mm), k1) || k1 != key) return false;
-  u = UnlzProgram{2u, 0u, mm, (U32)key[1]};
+  u = StreamProgram{2, 0u, mm, (U32)key[1]};
   return true;
 }
-// ZPAQ_AMD_DEVICE_UNLZ: 0 never, 1 always, unset (2): when lz_unlz_pays says so (device/engine.hpp)
-int device_unlz_mode() {
-  const char* v = getenv("ZPAQ_AMD_DEVICE_UNLZ");
+// A route's knob -- ZPAQ_AMD_DEVICE_UNLZ, ZPAQ_AMD_DEVICE_UNBWT, ZPAQ_AMD_DEVICE_UNE8 --: 0 never, 1 always, unset (2): when the
+// route's rule says so (lz_unlz_pays, bwt_unbwt_pays, e8_une8_pays: device/engine.hpp)
+int device_route_mode(const char* knob) {
+  const char* v = getenv(knob);
   if (!v || !*v) return 2;
   return v[0] == '0' ? 0 : 1;
 }
 // The inverse BWT without E8E9 at args[0] <= 4 (pcomp_bwt(arg0, false): the byte rides in the list's word), recognised the same
 // way; ph and pm are both args[0] + 20.
-bool unbwt_program(const std::vector<U8>& key, U32& mbits) {
+bool unbwt_program(const std::vector<U8>& key, StreamProgram& u) {
   if (key.size() < 3 || key[0] != key[1]) return false;
   const int a0 = (int)key[1] - 20;
   if (a0 < 0 || a0 > 4) return false;
   std::vector<U8> k;
   if (!unlz_generated(a0, ",3", k) || k != key) return false;
-  mbits = key[1];
+  u = StreamProgram{3, 0u, 0u, (U32)key[1]};
   return true;
-}
-// ZPAQ_AMD_DEVICE_UNBWT: 0 never, 1 always, unset (2): when bwt_unbwt_pays says so (device/engine.hpp)
-int device_unbwt_mode() {
-  const char* v = getenv("ZPAQ_AMD_DEVICE_UNBWT");
-  if (!v || !*v) return 2;
-  return v[0] == '0' ? 0 : 1;
 }
 // The programs of the E8E9 methods -- the filter alone (",4": ph = pm = 0, the same program whatever args[0]), in front of LZ77
 // level 1 (",5") and level 2 (",6,mm"), in front of the BWT at args[0] <= 4 (",7") -- recognised the same way.
-struct Une8Program { int kind; U32 rb, min_match, mbits; };
-bool une8_program(const std::vector<U8>& key, Une8Program& u) {
+bool une8_program(const std::vector<U8>& key, StreamProgram& u) {
   if (key.size() < 3) return false;
   std::vector<U8> k1, k2;
   if (key[0] == 0 && key[1] == 0) {
     if (!unlz_generated(0, ",4", k1) || k1 != key) return false;
-    u = Une8Program{4, 0u, 0u, 0u};
+    u = StreamProgram{4, 0u, 0u, 0u};
     return true;
   }
   const int a0 = (int)key[1] - 20;
   if (a0 < 0 || a0 > 11) return false;
   if (key[0] == key[1]) {
     if (a0 > 4 || !unlz_generated(a0, ",7", k1) || k1 != key) return false;
-    u = Une8Program{7, 0u, 0u, (U32)key[1]};
+    u = StreamProgram{7, 0u, 0u, (U32)key[1]};
     return true;
   }
   if (key[0] != 0) return false;
-  if (unlz_generated(a0, ",5", k1) && k1 == key) { u = Une8Program{5, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
+  if (unlz_generated(a0, ",5", k1) && k1 == key) { u = StreamProgram{5, a0 > 4 ? (U32)(a0 - 4) : 0u, 0u, (U32)key[1]}; return true; }
   if (!unlz_generated(a0, ",6,1", k1) || !unlz_generated(a0, ",6,2", k2) || k1.size() != key.size() || k2.size() != key.size()) return false;
   size_t at = key.size(), differ = 0;
   for (size_t i = 0; i < key.size(); ++i) if (k1[i] != k2[i]) { at = i; ++differ; }
   if (differ != 1) return false;
   const U32 mm = key[at];
   if (!unlz_generated(a0, ",6," + std::to_string(mm), k1) || k1 != key) return false;
-  u = Une8Program{6, 0u, mm, (U32)key[1]};
+  u = StreamProgram{6, 0u, mm, (U32)key[1]};
   return true;
-}
-// ZPAQ_AMD_DEVICE_UNE8: 0 never, 1 always, unset (2): when e8_une8_pays says so (device/engine.hpp)
-int device_une8_mode() {
-  const char* v = getenv("ZPAQ_AMD_DEVICE_UNE8");
-  if (!v || !*v) return 2;
-  return v[0] == '0' ? 0 : 1;
 }
 }  // namespace
 
@@ -749,27 +738,29 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
     }
     size_t nprog = 0;
     for (auto& kv : by_prog) nprog += kv.second.size();
-    // The LZ77 inverses without E8E9 have a decoder of their own on the device (device/lz77_decode_kernel.h: a wavefront per
-    // segment, not a lane): a group of such segments goes there first when no route is forced -- ZPAQ_AMD_DEVICE_UNLZ=0|1 forces
-    // it off or on, unset follows lz_unlz_pays.  Segments it declines stay in their group and go on exactly as before.
-    const int unlz = mode ? 0 : device_unlz_mode();
-    if (unlz && nprog && engine_device_count() > 0) {
+    // The standard methods' inverses have decoders of their own on the device, and a group of such segments goes there first when
+    // no route is forced.  One route: `how` is its knob (device_route_mode), `match` recognises a group's program, `pays` is its
+    // rule for an unset knob, `decode` its engine call; its counter is stored only when the route is on.  Segments it declines
+    // stay in their group and go on exactly as before.
+    auto route = [&](int how, bool (*match)(const std::vector<U8>&, StreamProgram&), bool (*pays)(U64, U64),
+                     int (*decode)(const StreamProgram&, std::vector<StreamJob>&, std::string&), std::atomic<U32>& counter) {
+      if (!how || !nprog || engine_device_count() <= 0) return;
       U32 taken = 0;
       for (auto& kv : by_prog) {
         const std::vector<U8>& key = kv.first;
-        UnlzProgram u;
-        if (!unlz_program(key, u)) continue;
+        StreamProgram u;
+        if (kv.second.empty() || !match(key, u)) continue;
         const size_t skip = 3 + (key.size() - 2);
         U64 bytes = 0;
-        std::vector<UnlzJob> uj;
+        std::vector<StreamJob> uj;
         for (size_t i : kv.second) {
           const Seg& s = *segs[i];
-          uj.push_back(UnlzJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
+          uj.push_back(StreamJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
           bytes += s.decoded.size() - skip;
         }
-        if (unlz != 1 && !lz_unlz_pays(uj.size(), bytes)) continue;
+        if (how != 1 && !pays(uj.size(), bytes)) continue;
         std::string note;
-        if (engine_lz77_decode(u.level, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
+        if (decode(u, uj, note) != 1) continue;
         std::vector<size_t> left;
         for (size_t k = 0; k < uj.size(); ++k) {
           const size_t i = kv.second[k];
@@ -778,69 +769,23 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
         }
         kv.second.swap(left);
       }
-      g_last_unlz_segments.store(taken, std::memory_order_relaxed);
-    }
+      counter.store(taken, std::memory_order_relaxed);
+    };
+    // The LZ77 inverses without E8E9 (device/lz77_decode_kernel.h: a wavefront per segment, not a lane): ZPAQ_AMD_DEVICE_UNLZ=0|1
+    // forces the route off or on, unset follows lz_unlz_pays.
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ"), unlz_program, lz_unlz_pays,
+          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_lz77_decode((U32)u.kind, u.rb, u.min_match, u.mbits, uj, note); },
+          g_last_unlz_segments);
     // The inverse BWT without E8E9 likewise (device/bwt_decode_kernel.h: a counting sort per tile, the list ranked from every
     // 256th node at once): ZPAQ_AMD_DEVICE_UNBWT=0|1 forces it off or on, unset follows bwt_unbwt_pays.
-    const int unbwt = mode ? 0 : device_unbwt_mode();
-    if (unbwt && nprog && engine_device_count() > 0) {
-      U32 taken = 0;
-      for (auto& kv : by_prog) {
-        const std::vector<U8>& key = kv.first;
-        U32 mbits = 0;
-        if (kv.second.empty() || !unbwt_program(key, mbits)) continue;
-        const size_t skip = 3 + (key.size() - 2);
-        U64 bytes = 0;
-        std::vector<UnbwtJob> uj;
-        for (size_t i : kv.second) {
-          const Seg& s = *segs[i];
-          uj.push_back(UnbwtJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
-          bytes += s.decoded.size() - skip;
-        }
-        if (unbwt != 1 && !bwt_unbwt_pays(uj.size(), bytes)) continue;
-        std::string note;
-        if (engine_bwt_decode(mbits, uj, note) != 1) continue;
-        std::vector<size_t> left;
-        for (size_t k = 0; k < uj.size(); ++k) {
-          const size_t i = kv.second[k];
-          if (uj[k].status == 0) { on_device[i] = 1; ++taken; }
-          else { done[i].clear(); left.push_back(i); }
-        }
-        kv.second.swap(left);
-      }
-      g_last_unbwt_segments.store(taken, std::memory_order_relaxed);
-    }
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNBWT"), unbwt_program, bwt_unbwt_pays,
+          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_bwt_decode(u.mbits, uj, note); }, g_last_unbwt_segments);
     // The E8E9 methods likewise: their stage's decoder, then the inverse filter over its output on the device
     // (device/e8e9_kernel.h: the scan is serial only along short chains).  ZPAQ_AMD_DEVICE_UNE8=0|1 forces it off or on, unset
     // follows e8_une8_pays.
-    const int une8 = mode ? 0 : device_une8_mode();
-    if (une8 && nprog && engine_device_count() > 0) {
-      U32 taken = 0;
-      for (auto& kv : by_prog) {
-        const std::vector<U8>& key = kv.first;
-        Une8Program u;
-        if (kv.second.empty() || !une8_program(key, u)) continue;
-        const size_t skip = 3 + (key.size() - 2);
-        U64 bytes = 0;
-        std::vector<Une8Job> uj;
-        for (size_t i : kv.second) {
-          const Seg& s = *segs[i];
-          uj.push_back(Une8Job{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
-          bytes += s.decoded.size() - skip;
-        }
-        if (une8 != 1 && !e8_une8_pays(uj.size(), bytes)) continue;
-        std::string note;
-        if (engine_e8e9_decode(u.kind, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
-        std::vector<size_t> left;
-        for (size_t k = 0; k < uj.size(); ++k) {
-          const size_t i = kv.second[k];
-          if (uj[k].status == 0) { on_device[i] = 1; ++taken; }
-          else { done[i].clear(); left.push_back(i); }
-        }
-        kv.second.swap(left);
-      }
-      g_last_une8_segments.store(taken, std::memory_order_relaxed);
-    }
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNE8"), une8_program, e8_une8_pays,
+          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_e8e9_decode(u.kind, u.rb, u.min_match, u.mbits, uj, note); },
+          g_last_une8_segments);
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
       U32 taken = 0;
       for (auto& kv : by_prog) {

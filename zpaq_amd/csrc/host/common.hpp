@@ -25,6 +25,9 @@ struct Failure : public std::runtime_error {
 
 void set_last_error(const std::string& s);
 
+// x rounded up to a multiple of a (sizes and offsets of device buffers: a is 4, 16, 64, 256, ...)
+inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
 // ---- sha1.cpp ----
 void sha1_compress(U32 h[5], const U8* block64);   // one 64-byte block
 void postproc_set_step_limit(U64 steps);             // ZPAQL steps one call of a custom PCOMP program may take (0: 2^34)
