@@ -288,6 +288,23 @@ void zpq_sha1_force_portable(int yes);
  * this by itself for batches with 4 or more such blocks; ZPQ_E_UNSUPPORTED when the device declines (a buffer of 16 MiB
  * or more, more than 65 535 buffers, not enough memory) -- the library then sorts on the host. */
 int zpq_suffix_arrays_device(const uint8_t* const* in, const uint32_t* len, uint32_t n, uint32_t* const* out);
+/* ONE buffer of any length below 2^31 bytes through the wide sorter (device/sa_wide_kernel.h: no block id in the key, two rank
+ * fields of up to 31 bits, 32 bytes of device memory per byte): out receives n positions, the end of the string ordered before
+ * every byte.  ZPQ_E_UNSUPPORTED with a note in zpq_last_error when there is no device, the length is outside the range or the
+ * block does not fit the device budget; out is untouched then.  zpq_compress_blocks sends its sorting blocks of 2^24 bytes and
+ * more this way (ZPAQ_AMD_DEVICE_SORT_WIDE unset: from 16 MiB + 4096 bytes, the smallest size measured; 1: all of them; 0: never);
+ * ZPAQ_AMD_SORT_WIDE_FROM=<bytes>, read per call, moves that split (tests).  zpq_last_wide_sort_blocks: the blocks of this
+ * process's last zpq_compress_blocks call that the wide sorter sorted; zpq_last_wide_sort_rounds: the doubling rounds of this
+ * process's last wide sort. */
+int zpq_suffix_array_device_wide(const uint8_t* in, uint32_t n, uint32_t* out);
+uint32_t zpq_last_wide_sort_blocks(void);
+uint32_t zpq_last_wide_sort_rounds(void);
+/* zpq_preprocess_block for one buffer with the sort by the wide sorter, for any method whose pre-processor sorts suffixes and
+ * any n below 2^31: a BWT method's last column is made on the device, an LZ77 method is parsed by the host with the device's
+ * array.  Byte for byte zpq_preprocess_block's stream; *len is always reported and nothing is written when cap is short
+ * (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED for a method that does not sort suffixes, without a device, or when the device
+ * declines; `data` is then as it came (an E8E9 method's filter is taken back on every failure). */
+int zpq_preprocess_block_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint8_t* out, size_t cap, size_t* len);
 int zpq_suffix_array_host(const uint8_t* in, uint32_t n, uint32_t* out);      /* the host's sorter (SA-IS), one buffer */
 /* compressBlock's level->method expansion (libzpaq.cpp:7579-7691), including
  * level-5 period detection on the data.  Writes a NUL-terminated "x..." /

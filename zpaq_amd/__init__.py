@@ -108,6 +108,12 @@ def lib():
     L.zpq_fragment_device.argtypes = _frag
     L.zpq_fragment_limits.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.zpq_fragment_limits.restype = None
+    L.zpq_suffix_array_device_wide.argtypes = [_u8p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.zpq_preprocess_block_device_wide.argtypes = [C.c_char_p, _u8p, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.zpq_last_wide_sort_blocks.restype = C.c_uint32
+    L.zpq_last_wide_sort_blocks.argtypes = []
+    L.zpq_last_wide_sort_rounds.restype = C.c_uint32
+    L.zpq_last_wide_sort_rounds.argtypes = []
     L.zpq_last_fragment_rounds.restype = C.c_uint32
     L.zpq_last_fragment_rounds.argtypes = []
     L.zpq_fragment_analyze.restype = C.c_uint32
@@ -315,6 +321,41 @@ def lz77_serialize_device(xmethod: str, blocks: Sequence, tokens: Sequence, caps
     rc = lib().zpq_lz77_serialize_device(xmethod.encode(), IA, IL, TA, TN, n, OA, OC, OL)
     sizes = [int(x) for x in OL]
     return rc, [outs[i][:min(sizes[i], caps[i])].tobytes() for i in range(n)], sizes
+
+
+def suffix_array_device_wide(data, spare: int = 0, fill: int = 0):
+    """zpq_suffix_array_device_wide: the suffix array of one buffer of any length below 2^31 from the device's wide sorter.
+    Returns (return code, array -- n + spare entries of uint32, pre-filled with `fill`, as the call left them)."""
+    a = data if isinstance(data, np.ndarray) else _arr(data)
+    n = int(a.size)
+    src = a if n else np.zeros(1, np.uint8)
+    out = np.full(max(n + spare, 1), fill, np.uint32)
+    rc = lib().zpq_suffix_array_device_wide(_p(src), n, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return rc, out[:n + spare]
+
+
+def preprocess_block_device_wide(xmethod: str, data, cap: int, guard: int = 0, fill: int = 0):
+    """zpq_preprocess_block_device_wide: zpq_preprocess_block's stream of one buffer, the sort by the device's wide sorter.
+    `data` (a writable uint8 array, or bytes that are copied) is E8E9-filtered in place where the method says so.  `guard` bytes of
+    `fill` lie behind the `cap` bytes of output.  Returns (return code, the buffer -- cap + guard bytes, as the call left it --,
+    size)."""
+    a = data if isinstance(data, np.ndarray) else _arr(data)
+    n = int(a.size)
+    src = a if n else np.zeros(1, np.uint8)
+    out = np.full(max(int(cap) + guard, 1), fill, np.uint8)
+    ol = C.c_size_t(0)
+    rc = lib().zpq_preprocess_block_device_wide(xmethod.encode(), _p(src), n, _p(out), int(cap), C.byref(ol))
+    return rc, out[:int(cap) + guard].tobytes(), int(ol.value)
+
+
+def last_wide_sort_blocks() -> int:
+    """Blocks of the last compress_blocks call that the device's wide sorter sorted (ZPAQ_AMD_DEVICE_SORT_WIDE)."""
+    return int(lib().zpq_last_wide_sort_blocks())
+
+
+def last_wide_sort_rounds() -> int:
+    """Doubling rounds of this process's last wide sort."""
+    return int(lib().zpq_last_wide_sort_rounds())
 
 
 def postprocess_block(xmethod: str, stream, cap: Optional[int] = None):

@@ -402,6 +402,55 @@ int zpq_suffix_arrays_device(const uint8_t* const* in, const uint32_t* len, uint
   ZPQ_CATCH
 }
 
+// One buffer of any length below 2^31 through the wide sorter (device/sa_wide_kernel.h); out receives n entries.
+int zpq_suffix_array_device_wide(const uint8_t* in, uint32_t n, uint32_t* out) {
+  ZPQ_TRY
+  if ((!in || !out) && n) fail(ZPQ_E_ARG, "null argument");
+  if (n >= (1u << 31)) fail(ZPQ_E_UNSUPPORTED, "wide suffix sort on the device unavailable: block outside the wide sorter's range");
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "wide suffix sort on the device unavailable: no device");
+  SortOut so;
+  std::string note;
+  if (!engine_sort_wide(SortJob{in, n, 0u, 0u, 0u, 0u, 0u}, so, note, true)) fail(ZPQ_E_UNSUPPORTED, "wide suffix sort on the device unavailable: " + note);
+  if (n) memcpy(out, so.sa.data(), 4ull * n);
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+uint32_t zpq_last_wide_sort_blocks(void) { return last_wide_sort_blocks(); }
+uint32_t zpq_last_wide_sort_rounds(void) { return engine_last_wide_sort_rounds(); }
+
+// What zpq_preprocess_block makes of one buffer, the sort by the wide sorter: a BWT method's last column is emitted on the
+// device, an LZ77 method that sorts suffixes is parsed by the host with the device's array.  E8E9 is applied in place and taken
+// back on every failure exit, as in zpq_preprocess_blocks_device.
+int zpq_preprocess_block_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint8_t* out, size_t cap, size_t* len) {
+  ZPQ_TRY
+  if (!xmethod || (!data && n) || !len) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  (void)make_config(xmethod, args);
+  if (!preprocess_needs_suffix_array(args)) fail(ZPQ_E_UNSUPPORTED, "the method's pre-processor does not sort suffixes");
+  if (n >= (1u << 31)) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: block outside the wide sorter's range");
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: no device");
+  struct Unfilter {
+    uint8_t* data; uint32_t n; bool done = false, keep = false;
+    ~Unfilter() { if (done && !keep) e8e9_inverse(data, n); }
+  } guard{data, n};
+  if (args[1] > 4) { e8e9_forward(data, n); guard.done = true; }
+  std::vector<U8> pre;
+  if (n == 0) (void)preprocess_block(data, 0, args, pre, nullptr, true);
+  else {
+    SortOut so;
+    std::string note;
+    if (!engine_sort_wide(sort_job(data, n, args), so, note, false)) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
+    if ((args[1] & 3) == 3) pre.swap(so.bwt);
+    else (void)preprocess_block(data, n, args, pre, so.sa.data(), true);
+  }
+  *len = pre.size();                                      // (the size is reported also when the buffer is too small)
+  if (pre.size() > cap) fail(ZPQ_E_OVERFLOW, "output buffer too small");
+  if (!pre.empty()) memcpy(out, pre.data(), pre.size());
+  guard.keep = true;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
 int zpq_expand_method(const char* method, const uint8_t* data, uint32_t n, char* out, size_t cap) {
   ZPQ_TRY
   const std::string m = expand_method(method ? method : "", data, n);

@@ -78,7 +78,7 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
 // codes: LZBuffer's codes are written on the device as well (device/lz77_codes_kernel.h) -- a block of kind 1 / 2 then comes back
 // as its finished stream in SortOut::codes (coded = true) and its list of matches is not downloaded.
 struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0, rb = 0; };   // (min_match2, ht_bits: hash_job; rb: the coder)
-struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; };
+struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; std::vector<U32> sa; };   // (sa: engine_sort_wide)
 // codes: 0 the lists come back; 1 the streams; 2 the streams when that pays -- decided per batch once the sizes are known, by
 // lz_codes_pay below (DESIGN 4.5.2 has the measurement behind it)
 bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes = 0);
@@ -95,6 +95,19 @@ inline SortJob sort_job(const U8* data, U32 n, const int args[9]) {
   j.rb = lz_offset_rb(args);
   return j;
 }
+// ONE block of any length below 2^31 through the wide sorter (device/sa_wide_kernel.h, DESIGN 4.5.7: no block id in the key, two
+// rank fields of up to 31 bits).  A block of kind 3 comes back as its BWT stream in out.bwt (n + 5 bytes, emitted on the device
+// from the ranks) unless want_sa; every other block, and every block with want_sa, as its suffix array in out.sa -- the host
+// parses or transforms with it.  false + note when the device declines (the block, its array or column and 32 bytes of workspace
+// per byte within the engine's budget): nothing was launched, the host sorts.
+bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa);
+U32 engine_last_wide_sort_rounds();    // doubling rounds of this process's last engine_sort_wide call that sorted
+// Whether a sorting block of n bytes takes the wide route when ZPAQ_AMD_DEVICE_SORT_WIDE is unset.  The rule, fixed before the
+// measurement: from the smallest measured block size at which the route beat the host's sorter in all three alternations on
+// every kind of data, never below 2^24 bytes.  That size is the smallest one measured, 16 MiB + 4096: 20 to 49 times faster
+// end to end on text, records and random bytes, 1.7 to 2.1 times on zeros (26 rounds), at every size up to 64 MiB - 4096
+// (DESIGN 4.5.7 has the table).
+inline bool sa_wide_pays(U64 n) { return n >= (16ull << 20) + 4096; }
 // The LZ77 parse through LZBuffer's hash table (args[5] - args[0] < 21: method 1, method 2 below type 64, ...) for a whole batch on
 // the device (device/lz77_hash_kernel.h): every block comes back as its list of matches, like the kind 1 / 2 blocks of
 // engine_sort_preprocess.  Same buffers, same contract: false + note when the device declines or fails (then the host parses),

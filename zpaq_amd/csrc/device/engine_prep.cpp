@@ -104,6 +104,53 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
   return true;
 }
 
+// The wide sorter for one block (device/sa_wide_kernel.h): the block up, the doubling rounds, then either the BWT's last column
+// straight from the ranks (kind 3 unless the caller wants the array: n + 5 bytes come back) or the array (4 n bytes; the host
+// parses or transforms with it).  Everything the call holds on the device is summed against the budget before anything is
+// launched.  Blocks go one after another on the engine's stream.
+static std::atomic<U32> g_last_wide_rounds{0};
+U32 engine_last_wide_sort_rounds() { return g_last_wide_rounds.load(std::memory_order_relaxed); }
+
+bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa) {
+  out = SortOut();
+  const uint64_t n = job.n;
+  if (!n) return true;
+  if (n >= (1ull << 31)) { note = "block outside the wide sorter's range"; return false; }
+  if (job.kind > 3) { note = "unknown pre-processor kind"; return false; }
+  const bool bwt = job.kind == 3 && !want_sa;
+  EngineCall call;
+  Engine& e = call.e;
+  const size_t ws = sa_wide_workspace_bytes(n);
+  const uint64_t in_bytes = align_up(n, 256);
+  const uint64_t out_bytes = (bwt ? 256 + n + 1 : 4 * n) + 256;       // (BWT: the index word in front of the column)
+  if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "suffix sort workspace exceeds the device budget"; return false; }
+  e.io_in.ensure(in_bytes + 64);
+  e.io_out.ensure(out_bytes);
+  e.arena.ensure(ws);
+  HIP_CHECK(hipMemcpyAsync(e.io_in.p, job.data, n, hipMemcpyHostToDevice, e.stream));
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  uint32_t rounds = 0;
+  const uint32_t* d_rank = nullptr;
+  hipError_t rc = build_suffix_array_wide((const uint8_t*)e.io_in.p, (uint32_t)n, bwt ? nullptr : (uint32_t*)ob, e.arena.p, e.arena.cap, e.stream, &rounds, &d_rank);
+  if (rc == hipSuccess && bwt) rc = launch_bwt_wide((const uint8_t*)e.io_in.p, d_rank, (uint32_t)n, ob + 256, (uint32_t*)ob, e.stream);
+  if (launch_failed(rc, "device wide suffix sort failed: ", note)) return false;
+  if (bwt) {
+    uint32_t idx = 0;
+    out.bwt.resize((size_t)n + 5);
+    HIP_CHECK(hipMemcpyAsync(out.bwt.data(), ob + 256, (size_t)n + 1, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipMemcpyAsync(&idx, ob, 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    for (int k = 0; k < 4; ++k) { out.bwt[(size_t)n + 1 + k] = (U8)idx; idx >>= 8; }
+  } else {
+    out.sa.resize((size_t)n);
+    HIP_CHECK(hipMemcpyAsync(out.sa.data(), ob, 4 * n, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+  }
+  g_last_wide_rounds.store(rounds, std::memory_order_relaxed);
+  note = "device (wide), " + std::to_string(rounds) + " doubling rounds";
+  return true;
+}
+
 // A block's entry in the table of the parse and code stages: where it lies, its kind, the coder's parameters, its token slots
 // (tok_off for every block: the coder's item slots are found by it).  The parse stages add their search parameters.
 static LzBlock lz_block(uint64_t off, uint32_t n, uint32_t kind, uint32_t min_match, uint32_t rb, uint64_t tok_off, uint32_t tok_cap) {

@@ -19,6 +19,16 @@ struct LzCodes { uint64_t nslots = 0; uint64_t* pos = nullptr; void* tmp = nullp
 // to back (block b's at d_sa + off[b]); max_len < 2^24, nblocks < 65536, total < 2^32.  Synchronises `st` once per round.
 hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off, uint32_t nblocks, uint64_t total, uint32_t max_len,
                                uint32_t* d_sa, void* ws, size_t ws_bytes, hipStream_t st, uint32_t* rounds_out, SaSideArrays* side = nullptr);
+// The wide sorter (device/sa_wide_kernel.h): ONE block of 1 <= n < 2^31 bytes at d_in, the key two rank fields of
+// sa_wide_rank_bits(n) bits (rank_bits != 0 forces a wider field: tests).  ws: sa_wide_workspace_bytes(n) bytes -- 32 per element
+// and the library's scratch.  d_sa receives the array, or is null when the caller goes on from the ranks: *rank_out points at
+// them in the workspace (rank[i] - 1 = position of suffix i in the array).  Synchronises `st` once per round.
+size_t sa_wide_workspace_bytes(uint64_t n);
+hipError_t build_suffix_array_wide(const uint8_t* d_in, uint32_t n, uint32_t* d_sa, void* ws, size_t ws_bytes, hipStream_t st, uint32_t* rounds_out,
+                                   const uint32_t** rank_out = nullptr, unsigned rank_bits = 0);
+// ... and the BWT's last column from those ranks, in preprocess_block's layout: n + 1 bytes at d_out, the index of the whole
+// string at d_idx[0]
+hipError_t launch_bwt_wide(const uint8_t* d_in, const uint32_t* d_rank, uint32_t n, uint8_t* d_out, uint32_t* d_idx, hipStream_t st);
 // Behind the sort, for the same batch (device/lz77_kernel.h): the LZ77 parse of the blocks of kind 1 / 2 -- 16 bytes of decisions
 // per element in `res`, then the matches taken in toks[blocks[b].tok_off ..) and their number in counts[b] -- and the BWT of
 // the blocks of kind 3 (n + 1 bytes at bwt_out + off + b, the index of the whole string in bwt_idx[b]).  in_all: the blocks'

@@ -12,8 +12,9 @@
 //   The kernels' bodies and the loop's two decisions are in device/sa_kernel.h (the emulator runs them: tests/emu/sa_emu_main.cpp).
 //
 // Each round streams the arrays a few times at HBM rate (radix sort of 64-bit keys + 32-bit values, one gather, one
-// scan, one scatter): bandwidth work, no MFMA.  Blocks of up to 2^24 bytes and 65 535 blocks per call; the caller
-// (host/blocks.cpp) keeps the host's SA-IS for anything else and for small batches.
+// scan, one scatter): bandwidth work, no MFMA.  Blocks below 2^24 bytes and 65 535 blocks per call; a block of 2^24 bytes
+// and more is sorted alone by the wide sorter below (device/sa_wide_kernel.h: no block id, rank fields of up to 31 bits); the
+// caller (host/blocks.cpp) keeps the host's SA-IS for small batches and for what the device declines.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -30,6 +31,7 @@
 #include "lz77_kernel.h"
 #include "sa_kernel.h"
 #include "sa_kernels.h"
+#include "sa_wide_kernel.h"
 
 namespace zpq {
 
@@ -53,6 +55,18 @@ __global__ __launch_bounds__(256) void sa_invert_kernel(const uint32_t* rank, co
 }
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+__global__ __launch_bounds__(256) void sa_wide_init_kernel(const uint8_t* in, uint32_t n, uint32_t* rank) { sa_wide_init_body(in, n, rank); }
+__global__ __launch_bounds__(256) void sa_wide_keys_kernel(const uint32_t* rank, uint32_t n, uint32_t h, uint32_t w, uint64_t* keys, uint32_t* vals) {
+  sa_wide_keys_body(rank, n, h, w, keys, vals);
+}
+__global__ __launch_bounds__(256) void sa_wide_rename_kernel(const uint32_t* vals, const uint32_t* scan, uint32_t n, uint32_t* rank) {
+  sa_wide_rename_body(vals, scan, n, rank);
+}
+__global__ __launch_bounds__(256) void sa_wide_invert_kernel(const uint32_t* rank, uint32_t n, uint32_t* sa) { sa_wide_invert_body(rank, n, sa); }
+__global__ __launch_bounds__(256) void bwt_wide_kernel(const uint8_t* in, const uint32_t* rank, uint32_t n, uint8_t* out, uint32_t* idx) {
+  bwt_wide_body(in, rank, n, out, idx);
+}
 
 __global__ __launch_bounds__(256) void lz77_search_kernel(const uint8_t* in_all, const uint32_t* sa_all, const uint32_t* rank_all, const uint16_t* blk,
                                                           const LzBlock* blocks, uint64_t total, uint4* res) {
@@ -193,6 +207,76 @@ hipError_t build_suffix_arrays(const uint8_t* const* d_in, const uint64_t* d_off
   hipLaunchKernelGGL(sa_invert_kernel, dim3(g), dim3(256), 0, st, rank, blk, d_off, total, d_sa);
   if (rounds_out) *rounds_out = rounds;
   if (side) { side->rank = rank; side->blk = blk; }
+  return hipGetLastError();
+}
+
+// The wide sorter (device/sa_wide_kernel.h): one block of 1 <= n < 2^31 bytes.  Keys x 2, values x 2 (the sort's double
+// buffers: the library ping-pongs between them and needs no copies of its own), rank, flags / scan -- 32 bytes per element --
+// and the library's scratch.  No element-to-block map.
+size_t sa_wide_workspace_bytes(uint64_t n) {
+  size_t sort_tmp = 0, scan_tmp = 0;
+  rocprim::double_buffer<uint64_t> k((uint64_t*)nullptr, (uint64_t*)nullptr);
+  rocprim::double_buffer<uint32_t> v((uint32_t*)nullptr, (uint32_t*)nullptr);
+  (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, k, v, (size_t)n, 0, 64);
+  (void)rocprim::inclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, rocprim::plus<uint32_t>());
+  const size_t a = (size_t)((n + 63) & ~63ull);
+  return a * (8 + 8 + 4 + 4 + 4 + 4) + (sort_tmp > scan_tmp ? sort_tmp : scan_tmp) + 4096;
+}
+
+// d_in: the block on the device.  d_sa (may be null: the ranks are all the caller wants) receives the array.  *rank_out: the
+// final ranks in the workspace (rank[i] - 1 = position of suffix i in the array), valid until the workspace is used again.
+// rank_bits: 0 = sa_wide_rank_bits(n); a test forces a wider field.  Synchronises `st` once per round.
+hipError_t build_suffix_array_wide(const uint8_t* d_in, uint32_t n, uint32_t* d_sa, void* ws, size_t ws_bytes, hipStream_t st, uint32_t* rounds_out,
+                                   const uint32_t** rank_out, unsigned rank_bits) {
+  if (rounds_out) *rounds_out = 0;
+  if (!n) return hipSuccess;
+  const unsigned r = rank_bits ? rank_bits : sa_wide_rank_bits(n);
+  if (n >= (1u << 31) || r > 32 || r < sa_wide_rank_bits(n) || ws_bytes < sa_wide_workspace_bytes(n)) return hipErrorInvalidValue;
+  const size_t a = (size_t)(((uint64_t)n + 63) & ~63ull);
+  uint8_t* p = (uint8_t*)ws;
+  uint64_t* keys = (uint64_t*)p; p += a * 8;
+  uint64_t* keys2 = (uint64_t*)p; p += a * 8;
+  uint32_t* vals = (uint32_t*)p; p += a * 4;
+  uint32_t* vals2 = (uint32_t*)p; p += a * 4;
+  uint32_t* rank = (uint32_t*)p; p += a * 4;
+  uint32_t* flags = (uint32_t*)p; p += a * 4;
+  p = (uint8_t*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
+  void* tmp = p;
+  const size_t tmp_bytes = ws_bytes - (size_t)(p - (uint8_t*)ws);
+  const unsigned g = grid_for(n);
+  hipLaunchKernelGGL(sa_wide_init_kernel, dim3(g), dim3(256), 0, st, d_in, n, rank);
+  uint32_t h = 1, rounds = 0;
+  for (;; h <<= 1) {
+    const unsigned w = sa_wide_field_bits(r, h);
+    hipLaunchKernelGGL(sa_wide_keys_kernel, dim3(g), dim3(256), 0, st, (const uint32_t*)rank, n, h, (uint32_t)w, keys, vals);
+    rocprim::double_buffer<uint64_t> kb(keys, keys2);
+    rocprim::double_buffer<uint32_t> vb(vals, vals2);
+    size_t need = tmp_bytes;
+    hipError_t e = rocprim::radix_sort_pairs(tmp, need, kb, vb, (size_t)n, 0, 2 * w, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sa_flags_kernel, dim3(g), dim3(256), 0, st, (const uint64_t*)kb.current(), (uint64_t)n, flags);
+    need = tmp_bytes;
+    e = rocprim::inclusive_scan(tmp, need, flags, flags, (size_t)n, rocprim::plus<uint32_t>(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sa_wide_rename_kernel, dim3(g), dim3(256), 0, st, (const uint32_t*)vb.current(), (const uint32_t*)flags, n, rank);
+    ++rounds;
+    uint32_t names = 0;                                              // the last prefix sum
+    e = hipMemcpyAsync(&names, flags + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return e;
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    if (sa_round_is_last(names, n, h, n)) break;
+  }
+  if (d_sa) hipLaunchKernelGGL(sa_wide_invert_kernel, dim3(g), dim3(256), 0, st, (const uint32_t*)rank, n, d_sa);
+  if (rounds_out) *rounds_out = rounds;
+  if (rank_out) *rank_out = rank;
+  return hipGetLastError();
+}
+
+// the BWT's last column of the block build_suffix_array_wide has just ranked: n + 1 bytes at d_out, the index at d_idx[0]
+hipError_t launch_bwt_wide(const uint8_t* d_in, const uint32_t* d_rank, uint32_t n, uint8_t* d_out, uint32_t* d_idx, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(bwt_wide_kernel, dim3(grid_for(n)), dim3(256), 0, st, d_in, d_rank, n, d_out, d_idx);
   return hipGetLastError();
 }
 

@@ -193,6 +193,9 @@ void parallel_blocks(size_t n, F&& fn) {
 
 }  // namespace
 
+static std::atomic<U32> g_last_wide_sort_blocks{0};
+U32 last_wide_sort_blocks() { return g_last_wide_sort_blocks.load(std::memory_order_relaxed); }
+
 // From what batch on the hash-table LZ77 parse goes to the device (DESIGN 4.5 has the measurements behind it)
 static const size_t kHashParseMinBlocks = 4;
 static const U64 kHashParseMinBytes = 1u << 20;
@@ -249,7 +252,7 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
   });
   // Blocks whose pre-processor sorts suffixes (byte-aligned LZ77 with a suffix array: level 3; BWT): one suffix sort for
   // all of them on the device when there are enough to fill it (device/sa_kernels.hip), the host's SA-IS per block otherwise
-  // or when the device declines (no GPU, blocks of 16 MiB and more, not enough memory).  The array is canonical: either
+  // or when the device declines (no GPU, not enough memory).  The array is canonical: either
   // source gives the reference's parse.  E8E9 comes first where the method has it (it changes the bytes that are sorted).
   // ... and behind the sort, on the device as well (device/lz77_kernel.h): the LZ77 parse comes back as a list of matches the
   // host only has to write LZBuffer's codes for, the BWT as its bytes -- 16 bytes per match or n + 5 bytes over PCIe instead
@@ -262,9 +265,37 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
   std::vector<SortOut> dev_pre(nb);
   std::vector<char> have_pre(nb, 0);
   {
+    // Blocks of 2^24 bytes and more are beyond the batched sorter's 24-bit rank fields; they go to the wide sorter
+    // (device/sa_wide_kernel.h), each on its own -- one such block fills the device, the four-block threshold below
+    // belongs to the batched sorter.  ZPAQ_AMD_DEVICE_SORT_WIDE=0|1 forces that route off or on, unset follows sa_wide_pays;
+    // ZPAQ_AMD_SORT_WIDE_FROM=<bytes> moves the split (tests: small blocks through the wide route).  A BWT block comes back as its
+    // stream, an LZ77 block as its array and the host parses with it; with ZPAQ_AMD_DEVICE_PARSE=0 the array comes back either
+    // way.  A block the route does not take, or that the device declines or fails on, is sorted by the host as before.  The other
+    // sorting blocks are a batch of their own.
+    U64 wide_from = 1u << 24;
+    if (const char* v = getenv("ZPAQ_AMD_SORT_WIDE_FROM")) { const long long x = atoll(v); if (x > 0) wide_from = (U64)x; }
+    const char* wk = getenv("ZPAQ_AMD_DEVICE_SORT_WIDE");
+    const int wide_mode = !wk || !wk[0] ? 2 : (wk[0] == '0' ? 0 : 1);
+    const char* pk = getenv("ZPAQ_AMD_DEVICE_PARSE");
+    const bool dev_parse = !pk || pk[0] != '0';
     std::vector<size_t> sorting;
     U64 sort_bytes = 0;
-    for (size_t b = 0; b < nb; ++b) if (front[b].sorts) { sorting.push_back(b); sort_bytes += in[b].n; }
+    U32 wide_blocks = 0;
+    for (size_t b = 0; b < nb; ++b) {
+      if (!front[b].sorts) continue;
+      const bool take = in[b].n >= wide_from && (wide_mode == 1 || (wide_mode == 2 && in[b].n >= (1u << 24) && sa_wide_pays(in[b].n)));
+      if (!take && in[b].n < (1u << 24)) { sorting.push_back(b); sort_bytes += in[b].n; continue; }
+      if (!take || engine_device_count() <= 0) { front[b].sorts = false; continue; }   // nothing was done up front: preprocess_block does it all
+      if (front[b].args[1] > 4) e8e9_forward(in[b].data, in[b].n);
+      SortOut so;
+      std::string note;
+      bool got = false;
+      try { got = engine_sort_wide(sort_job(in[b].data, in[b].n, front[b].args), so, note, !dev_parse); } catch (const Failure&) { got = false; }   // (any device trouble: the host sorts)
+      if (got && !so.bwt.empty()) { dev_pre[b] = std::move(so); have_pre[b] = 1; }
+      else if (got) dev_sa[b].swap(so.sa);
+      wide_blocks += got;                            // (front[b].sorts stays true: E8E9 is done either way)
+    }
+    g_last_wide_sort_blocks.store(wide_blocks, std::memory_order_relaxed);
     // the device sorter's range is known up front (blocks below 16 MiB, 2 GiB per batch, 65535 blocks): a batch outside it
     // is left to the host sorter before anything is touched
     bool in_range = sorting.size() <= 65535 && sort_bytes < (1ull << 31);

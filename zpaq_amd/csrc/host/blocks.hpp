@@ -60,6 +60,7 @@ std::vector<U8> decode_payload(const std::vector<U8>& header, const U8* payload,
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink);
 
 // segments of this process's last decode_archive call that device/lz77_decode_kernel.h decoded
+U32 last_wide_sort_blocks();          // sorting blocks of this process's last compress_blocks call that the wide sorter sorted
 U32 last_device_unlz_segments();
 // ... that device/bwt_decode_kernel.h decoded
 U32 last_device_unbwt_segments();
