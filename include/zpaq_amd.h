@@ -383,12 +383,27 @@ uint32_t zpq_last_device_unlz_segments(void);
  * workspace per stream byte, the tile histograms, the splitter tables and the outputs within the device budget). */
 int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
                           uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
-/* Segments of this process's last zpq_decompress call that device/bwt_decode_kernel.h decoded.  A segment qualifies when its
- * block has one segment and carries, byte for byte, the BWT program without E8E9 that compressBlock's methods generate at
- * args[0] <= 4 (the BWT branches of methods 3 and 4, x.,3..) with ph = pm = args[0] + 20; E8E9 variants, args[0] > 4, custom
- * programs and blocks of several segments never do.  ZPAQ_AMD_DEVICE_UNBWT=0|1 forces the route off or on for qualifying
- * segments; unset it is off: it is taken only from a measured group size of 64 segments or more at which it beat both other
- * routes, and no measurement exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.
+/* The same for the program of a BWT method at args[0] 5 .. 11 -- xN,3 and, behind the inverse E8E9 filter, xN,7 for N in 5 .. 11,
+ * the blocks of 16 MiB and more that the small decoder's 24-bit list word cannot hold (device/bwt_decode_wide_kernel.h, DESIGN
+ * 4.5.8: 8 bytes per node, the splitter list ranked over second-level splitters).  The contract is zpq_bwt_decode_device's, per
+ * stream: status 0 -- out[b] holds, byte for byte, what zpq_postprocess_block makes of stream b with that method; 1 declined,
+ * out[b] untouched -- a stream shorter than 5 bytes or outside the rule, n + 257 > 2^(args[0] + 20), a path that has not n nodes,
+ * for xN,7 a block the filter gave up, and a stream whose workspace does not fit the device budget alone.  A stream of any
+ * admitted length is taken, a small one too.  A batch whose outputs exceed 2 GiB or whose workspace (8 bytes per stream byte, 1
+ * KiB per tile, the two splitter tables, the streams and the outputs) exceeds the budget is cut into consecutive sub-batches.
+ * ZPQ_E_OVERFLOW with every size reported and nothing launched when an admitted stream does not fit its buffer;
+ * ZPQ_E_UNSUPPORTED with a note without a device, for another method (args[0] <= 4 among them: zpq_bwt_decode_device /
+ * zpq_e8e9_decode_device), or when nothing of the batch fits the budget. */
+int zpq_bwt_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                               uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that device/bwt_decode_kernel.h or, for the program at args[0] 5 .. 11,
+ * device/bwt_decode_wide_kernel.h decoded.  A segment qualifies when its block has one segment and carries, byte for byte, the
+ * BWT program without E8E9 that compressBlock's methods generate (the BWT branches of methods 3 and 4, x.,3..) with ph = pm =
+ * args[0] + 20; E8E9 variants (zpq_last_device_une8_segments counts those), custom programs and blocks of several segments
+ * never do.  ZPAQ_AMD_DEVICE_UNBWT=0|1 forces the route off or on for qualifying segments.  Unset, at args[0] <= 4 it is off:
+ * it is taken only from a measured group size of 64 segments or more at which it beat both other routes, and no measurement
+ * exists yet.  Unset, at args[0] 5 .. 11 it is on for a group of 2^24 + 4 097 stream bytes or more, the smallest
+ * size measured (bwt_unbwt_wide_pays), and off below.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.
  * The bytes are the same either way. */
 uint32_t zpq_last_device_unbwt_segments(void);
 /* The same for a batch of streams of an E8E9 method: args[1] = 4 (the filter alone: the stream is the filtered block), 5 / 6 (in
@@ -406,7 +421,8 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
                            uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
 /* Segments of this process's last zpq_decompress call that went that way.  A segment qualifies when its block has one segment
  * and carries, byte for byte, one of the E8E9 programs compressBlock's methods generate: the filter alone (x.,4..), in front of
- * LZ77 (x.,5.., x.,6..) or in front of the BWT at args[0] <= 4 (x.,7..); custom programs, the BWT at args[0] > 4 and blocks of
+ * LZ77 (x.,5.., x.,6..) or in front of the BWT (x.,7..; at args[0] 5 .. 11 the stage in front is the wide BWT decoder of
+ * zpq_bwt_decode_device_wide, and with the knob unset the route is off: no such group has been timed); custom programs and blocks of
  * several segments never do.  ZPAQ_AMD_DEVICE_UNE8=0|1 forces the route off or on for qualifying segments; unset it is off: it
  * is taken only from a measured group size of 64 segments or more at which it beat both other routes, and no measurement
  * exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  ZPAQ_AMD_DEVICE_UNLZ and

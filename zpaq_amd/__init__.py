@@ -91,6 +91,7 @@ def lib():
     L.zpq_last_device_unlz_segments.argtypes = []
     L.zpq_bwt_decode_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    L.zpq_bwt_decode_device_wide.argtypes = L.zpq_bwt_decode_device.argtypes
     L.zpq_last_device_unbwt_segments.restype = C.c_uint32
     L.zpq_last_device_unbwt_segments.argtypes = []
     L.zpq_e8e9_decode_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
@@ -414,6 +415,24 @@ def bwt_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guar
     OL = (C.c_size_t * n)()
     ST = (C.c_int32 * n)()
     rc = lib().zpq_bwt_decode_device(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
+    return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
+
+
+def bwt_decode_device_wide(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
+    """zpq_bwt_decode_device_wide: a batch of BWT streams of the program at args[0] 5 .. 11 (xN,3, and xN,7 behind the inverse E8E9
+    filter) back into their blocks on the device.  caps = the output capacities; `guard` bytes of `fill` lie behind each.  Returns
+    (return code, buffers -- cap + guard bytes each, as the call left them --, sizes, statuses: 0 decoded, 1 declined)."""
+    n = len(streams)
+    ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in streams]
+    caps = [int(c) for c in caps]
+    outs = [np.full(max(c + guard, 1), fill, np.uint8) for c in caps]
+    IA = (_u8p * n)(*[_p(a) for a in ins])
+    IL = (C.c_uint32 * n)(*[len(x) for x in streams])
+    OA = (_u8p * n)(*[_p(a) for a in outs])
+    OC = (C.c_size_t * n)(*caps)
+    OL = (C.c_size_t * n)()
+    ST = (C.c_int32 * n)()
+    rc = lib().zpq_bwt_decode_device_wide(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
     return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
 
 

@@ -715,6 +715,17 @@ int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, con
 
 uint32_t zpq_last_device_unbwt_segments(void) { return last_device_unbwt_segments(); }
 
+// ... BWT streams of the program at args[0] 5 .. 11, without E8E9 or behind it (device/bwt_decode_wide_kernel.h)
+int zpq_bwt_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                               size_t* outlen, int32_t* status) {
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        return xm[0] == '0' || (args[1] != 3 && args[1] != 7) || args[0] < 5 || args[0] > 11 ? "not a BWT method (level 3, with or without E8E9) at args[0] 5 .. 11"
+                                                                                             : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) { return engine_bwt_decode_wide((U32)(args[0] + 20), args[1] == 7, jobs, note); });
+}
+
 // ... and streams of an E8E9 method (device/e8e9_kernel.h behind the stage's decoder)
 int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                            size_t* outlen, int32_t* status) {

@@ -159,6 +159,22 @@ int engine_bwt_decode(U32 mbits, std::vector<StreamJob>& jobs, std::string& note
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
 inline bool bwt_unbwt_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
+// The same for the program at args[0] 5 .. 11 (mbits 25 .. 31; device/bwt_decode_wide_kernel.h): the list's word is
+// a full position, so n goes up to 2^31 - 257; e8: the method is xN,7 and the inverse E8E9 filter runs over the outputs while
+// they are on the device, as for kind 7 of engine_e8e9_decode.  1 / 0 / -1 as for engine_bwt_decode, but a batch whose outputs
+// exceed 2 GiB or whose workspace (8 bytes per stream byte for the list, 1 KiB per tile, the two splitter tables, the streams
+// and the outputs) exceeds the budget is cut into consecutive sub-batches that each fit; only a stream that does not fit alone
+// is declined (status 1; -1 + note when nothing else was decoded).
+int engine_bwt_decode_wide(U32 mbits, bool e8, std::vector<StreamJob>& jobs, std::string& note);
+// Whether a group of qualifying xN,3 segments takes that route when ZPAQ_AMD_DEVICE_UNBWT is unset.  The
+// rule is the one of lz_unlz_pays, fixed before the measurement: from the smallest measured group size (bytes of admitted
+// output) at which the route beat both other settings in all three alternations (DESIGN 4.5.8 has the table).  That is the
+// smallest size measured, one block of 2^24 + 4 097 bytes: 17 ms against 2.2 s for the host's program and 18 s for the one-lane
+// kernel on text.  Groups below it were not measured and stay with the route they had unless the knob says 1.
+inline bool bwt_unbwt_wide_pays(U64 /*segments*/, U64 stream_bytes) { return stream_bytes >= (1ull << 24) + 4097; }
+// The same for xN,7 groups and ZPAQ_AMD_DEVICE_UNE8, by the same rule.  No xN,7 group has been timed -- neither the filter behind
+// the wide stage nor the windowed program it replaces -- so the route is off unless the knob says 1.
+inline bool bwt_une8_wide_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
 // Streams of the E8E9 methods back into their blocks on the device: kind = args[1], 5 / 6 the LZ77 decoder of level 1 / 2 (rb,
 // min_match, mbits as for engine_lz77_decode), 7 the BWT decoder (mbits as for engine_bwt_decode), 4 nothing -- then the inverse
 // filter over the stage's output while it is on the device (device/e8e9_kernel.h: candidates, seeds and breaks marked from the

@@ -328,6 +328,132 @@ static int bwt_decode_batch(U32 mbits, std::vector<StreamJob>& jobs, std::string
 }
 int engine_bwt_decode(U32 mbits, std::vector<StreamJob>& jobs, std::string& note) { return bwt_decode_batch(mbits, jobs, note, false); }
 
+// device/bwt_decode_wide_kernel.h for a batch of host streams: the program at args[0] 5 .. 11 (mbits 25 .. 31).  The order is
+// bwt_decode_batch's -- admit, size, report an overflow with every size and nothing launched, check the budget, launch, deliver --
+// but these blocks are large: a batch whose outputs exceed 2 GiB or whose workspace exceeds the budget is cut into consecutive
+// sub-batches that each fit (layout.h bwt_wide_cut), which run one after the other through the same buffers.  Only a stream that
+// does not fit alone is declined (status 1 + note; -1 when nothing else was decoded either).  After a failed launch nothing more
+// is started: that sub-batch and every stream behind it are declined.
+static int bwt_decode_wide_batch(U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
+  const size_t n = jobs.size();
+  if (!n) return 1;
+  for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
+  if (mbits < 25 || mbits > 31) { note = "batch outside the device decoder's range"; return -1; }
+  std::vector<size_t> who;                          // admitted stream k is jobs[who[k]]
+  std::vector<uint32_t> ns, idxs;
+  std::vector<char> empty(n, 0);
+  bool fits = true;
+  for (size_t i = 0; i < n; ++i) {
+    const StreamJob& j = jobs[i];
+    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
+    uint32_t sn = 0, sidx = 0;
+    if (!bwt_wide_stream_admitted(j.in, j.in_len, mbits, sn, sidx)) continue;
+    jobs[i].out_len = sn;
+    if (!j.vec && sn > j.cap) fits = false;
+    who.push_back(i);
+    ns.push_back(sn);
+    idxs.push_back(sidx);
+  }
+  if (!fits) return 0;
+  const size_t m = who.size();
+  bool some = false, left = false;
+  if (m) {
+    EngineCall call;
+    Engine& e = call.e;
+    // (the filter's own tables are about 8 bytes per 4 KiB tile: the cut leaves them 1/256 of the budget)
+    const uint64_t spare = (1u << 20) + (e8 ? e.budget / 256 : 0), held_limit = e.budget > spare ? e.budget - spare : 0;
+    bool broken = false;                              // a launch or the runtime failed: nothing more is started on the device
+    auto run = [&](size_t from, size_t end) -> bool {
+      const size_t mm = end - from;
+      std::vector<BwtStream> st(mm);
+      std::vector<uint32_t> s2(mm);
+      BwtWideNeed w;
+      for (size_t k = 0; k < mm; ++k) {
+        BwtStream& S = st[k];
+        memset(&S, 0, sizeof(S));
+        S.n = ns[from + k];
+        S.idx = idxs[from + k];
+        S.in_off = w.in_bytes;
+        S.link_off = w.nodes;
+        S.out_off = w.room;
+        S.tile_off = (uint32_t)w.tiles;
+        S.sp_off = (uint32_t)w.splits;
+        s2[k] = (uint32_t)w.splits2;
+        w.add(S.n, e8);
+      }
+      // the arena buffer (idle between batches): the list, the tile histograms, the two splitter tables, the stream tables, the statuses
+      Carve cv;
+      cv.take(8 * w.nodes);
+      const uint64_t o_hist = cv.take(1024 * w.tiles);
+      const uint64_t o_sp = cv.take(16 * w.splits);
+      const uint64_t o_sp2 = cv.take(16 * w.splits2);
+      const uint64_t o_st = cv.take(mm * sizeof(BwtStream));
+      const uint64_t o_s2 = cv.take(4 * mm);
+      const uint64_t o_res = cv.take(4 * mm);
+      const uint64_t ws = cv.at + 256;
+      uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
+      for (size_t k = 0; k < mm && e8; ++k) f_tiles += e8_tiles(st[k].n);
+      const uint64_t f_off = e8 ? align_up(w.room, 256) : w.room, f_ws = e8 ? une8_ws(mm, f_tiles).bytes : 0;
+      if (ws + w.in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return false; }
+      e.io_in.ensure(w.in_bytes + 64);
+      e.io_out.ensure(f_off + f_ws + 64);
+      e.arena.ensure(ws);
+      uint8_t* const ab = (uint8_t*)e.arena.p;
+      std::vector<HostItem> items(mm);
+      for (size_t k = 0; k < mm; ++k) items[k] = HostItem{jobs[who[from + k]].in, jobs[who[from + k]].in_len, st[k].in_off};
+      const auto staged = upload_staged(e, e.io_in.p, items, w.in_bytes, 4, false);
+      HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), mm * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
+      HIP_CHECK(hipMemcpyAsync(ab + o_s2, s2.data(), 4 * mm, hipMemcpyHostToDevice, e.stream));
+      const hipError_t rc = launch_bwt_decode_wide((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (const uint32_t*)(ab + o_s2), (uint32_t)mm,
+                                                   (uint32_t)w.tiles, (uint32_t)w.splits, (uint32_t)w.splits2, (uint32_t*)(ab + o_hist), (uint64_t*)ab,
+                                                   ab + o_sp, ab + o_sp2, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
+      if (launch_failed(rc, "device BWT decoder failed: ", note)) { broken = true; return false; }
+      std::vector<uint32_t> res(mm);
+      HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * mm, hipMemcpyDeviceToHost, e.stream));
+      HIP_CHECK(hipStreamSynchronize(e.stream));
+      if (e8) {
+        std::vector<E8Block> fb;
+        std::vector<size_t> fk;
+        std::vector<uint32_t> fst;
+        uint64_t tiles = 0;
+        for (size_t k = 0; k < mm; ++k) {
+          if (res[k] != 0) continue;
+          fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
+          fk.push_back(k);
+          tiles += e8_tiles(st[k].n);
+        }
+        if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { broken = note.find("budget") == std::string::npos; return false; }
+        for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
+      }
+      for (size_t k = 0; k < mm; ++k) {
+        StreamJob& j = jobs[who[from + k]];
+        if (res[k] != 0) { j.out_len = 0; continue; }
+        deliver(e, j, st[k].out_off, st[k].n);
+      }
+      HIP_CHECK(hipStreamSynchronize(e.stream));
+      for (size_t k = 0; k < mm; ++k) if (res[k] == 0) jobs[who[from + k]].status = 0;
+      return true;
+    };
+    for (size_t from = 0; from < m;) {
+      size_t end = bwt_wide_cut(ns.data(), m, from, 1ull << 31, held_limit, e8);
+      bool ok = end > from;
+      if (!ok) { note = "decoder workspace exceeds the device budget"; end = from + 1; }
+      else ok = run(from, end);
+      if (ok) some = true;
+      else { left = true; for (size_t k = from; k < end; ++k) jobs[who[k]].out_len = 0; }
+      from = end;
+      if (broken) {                                     // only a sub-batch beyond the budget lets the next one run
+        for (size_t k = from; k < m; ++k) jobs[who[k]].out_len = 0;
+        break;
+      }
+    }
+  }
+  if (left && !some) return declined(jobs);
+  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
+  return 1;
+}
+int engine_bwt_decode_wide(U32 mbits, bool e8, std::vector<StreamJob>& jobs, std::string& note) { return bwt_decode_wide_batch(mbits, jobs, note, e8); }
+
 // Streams of the E8E9 methods back into their blocks: the stage in front with the method's own parameters (kind 5 / 6: the LZ77
 // decoder, kind 7: the BWT decoder, kind 4: none -- the stream is the filtered block), then device/e8e9_kernel.h over its output
 // while that is still on the device.

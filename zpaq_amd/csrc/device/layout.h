@@ -268,6 +268,56 @@ static inline bool bwt_stream_admitted(const uint8_t* s, uint64_t len, uint32_t 
 static inline bool bwt_stream_empty(const uint8_t* s, uint64_t len) {      // what preprocess_block writes for an empty block
   return len == 5 && s[0] == 255u && !s[1] && !s[2] && !s[3] && !s[4];
 }
+// The wide form (device/bwt_decode_wide_kernel.h): what the program computes at args[0] 5 .. 11, where the list's word is a full
+// position and the byte is read from M.  The same stream, tiles and splitters; a node's word is 8 bytes ((uint64_t)byte << 32 |
+// node), and the splitter list is ranked like the node list: every kBwtStride2-th splitter index is a second-level splitter
+// (entry 0: splitter 0, the end; the last: the head).  A stream's second-level table starts at sp2_off[stream], an array beside
+// the BwtStream table.
+enum { kBwtStride2 = 256 };
+static inline uint32_t bwt_splitters2(uint32_t n) { return n / ((uint32_t)kBwtStride * (uint32_t)kBwtStride2) + 2u; }
+// Whether the wide form takes a stream: the rule, mbits 25 .. 31 (args[0] 5 .. 11), n + 257 <= 2^mbits -- so n <= 2^31 - 257.
+static inline bool bwt_wide_stream_admitted(const uint8_t* s, uint64_t len, uint32_t mbits, uint32_t& n, uint32_t& idx) {
+  if (len < 6 || mbits < 25u || mbits > 31u) return false;
+  const uint64_t n64 = len - 5;
+  if (n64 + 257u > (1ull << mbits)) return false;
+  const uint8_t* t = s + n64 + 1;
+  const uint32_t i = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+  if (i < 1u || i > n64 || s[i] != 255u) return false;
+  n = (uint32_t)n64;
+  idx = i;
+  return true;
+}
+// What a batch of wide streams holds on the device: the engine and the emulator's driver add up and place a batch with this.
+struct BwtWideNeed {
+  uint64_t streams = 0, in_bytes = 0, nodes = 0, tiles = 0, splits = 0, splits2 = 0, room = 0;
+  void add(uint32_t n, bool e8) {
+    ++streams;
+    in_bytes += ((uint64_t)n + 5u + 3u) & ~3ull;               // every stream starts on a word
+    nodes += (uint64_t)n + 1u;
+    tiles += bwt_tiles(n);
+    splits += bwt_splitters(n);
+    splits2 += bwt_splitters2(n);
+    room += e8 ? (((uint64_t)n + 15u) & ~15ull) : n;           // (e8_room: the filter's blocks start on a lane's 16 bytes)
+  }
+  // the bytes counted against the budget: the node words, 1 KiB per tile, the two splitter tables, the tables per stream, the
+  // streams and the outputs (each array starts on 256 bytes)
+  uint64_t bytes() const {
+    return 8u * nodes + 1024u * tiles + 16u * splits + 16u * splits2 + streams * (sizeof(BwtStream) + 8u) + in_bytes + room + 8u * 256u;
+  }
+};
+// The sub-batch that starts at admitted stream `from` (n[k]: its bytes): consecutive streams while the outputs stay within
+// out_limit and what the batch holds within held_limit.  Returns its end; `from` itself: that stream does not fit alone.
+static inline size_t bwt_wide_cut(const uint32_t* n, size_t m, size_t from, uint64_t out_limit, uint64_t held_limit, bool e8) {
+  BwtWideNeed w;
+  size_t k = from;
+  for (; k < m && k - from < 65535u; ++k) {
+    BwtWideNeed t = w;
+    t.add(n[k], e8);
+    if (t.room > out_limit || t.bytes() > held_limit) break;
+    w = t;
+  }
+  return k;
+}
 
 // The inverse E8E9 filter over blocks that lie in one device buffer, in place (device/e8e9_kernel.h)
 enum { kE8Lane = 16, kE8Tile = 4096 };                 // bytes per lane of the mark pass, per workgroup of 256 lanes

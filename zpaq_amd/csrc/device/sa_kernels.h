@@ -69,6 +69,13 @@ hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, ui
 // not n nodes and nothing of it was written.
 hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t ntiles, uint32_t nsplit, uint32_t* hist,
                              uint32_t* link, void* splitters, uint32_t* status, uint8_t* out_all, hipStream_t st);
+// ... of blocks of 16 MiB and more (device/bwt_decode_wide_kernel.h): the same for streams admitted by bwt_wide_stream_admitted --
+// 8 bytes per node in link, and nsplit2 entries of 16 bytes in splitters2, stream b's from sp2_off[b] (bwt_splitters2(n) each):
+// the scan takes four parts of a stream's tiles at once, and the splitter list is ranked over its own splitters instead of walked
+// by one lane.
+hipError_t launch_bwt_decode_wide(const uint8_t* in_all, const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t ntiles,
+                                  uint32_t nsplit, uint32_t nsplit2, uint32_t* hist, uint64_t* link, void* splitters, void* splitters2, uint32_t* status,
+                                  uint8_t* out_all, hipStream_t st);
 // The inverse E8E9 filter over blocks in one device buffer, in place (device/e8e9_kernel.h).  blocks[b] = {off, n, tile_off}: off a
 // multiple of 16 with the room behind the block rounded up to 16, ntiles = the sum of e8_tiles(n).  launch_une8_mark leaves in
 // cnt (2 * ntiles + 1 words) the exclusive prefix sums of the tiles' seed and break counts and zeroes status[0 .. nblocks); tmp:

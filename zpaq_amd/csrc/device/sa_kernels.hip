@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "bwt_decode_kernel.h"
+#include "bwt_decode_wide_kernel.h"
 #include "e8e9_kernel.h"
 #include "fragment_kernel.h"
 #include "lz77_codes_kernel.h"
@@ -131,6 +132,31 @@ __global__ __launch_bounds__(64) void unbwt_offsets_kernel(const BwtStream* stre
 __global__ __launch_bounds__(256) void unbwt_emit_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link, const uint4* sp,
                                                          const uint32_t* status, uint8_t* out_all) {
   unbwt_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
+}
+
+// device/bwt_decode_wide_kernel.h: the stages that differ for blocks of 16 MiB and more (the count is the small form's)
+__global__ __launch_bounds__(1024) void unbwt_wide_scan_kernel(const BwtStream* streams, uint32_t* hist) { unbwt_wide_scan_body(streams, hist); }
+__global__ __launch_bounds__(64) void unbwt_wide_link_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
+                                                             uint64_t* link) {
+  unbwt_wide_link_body(in_all, streams, nstreams, hist, link);
+}
+__global__ __launch_bounds__(256) void unbwt_wide_rank_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link, uint4* sp) {
+  unbwt_wide_rank_body(streams, nstreams, nsplit, link, sp);
+}
+__global__ __launch_bounds__(256) void unbwt_wide_rank2_kernel(const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t nsplit2,
+                                                               const uint4* sp, uint4* sp2) {
+  unbwt_wide_rank2_body(streams, sp2_off, nstreams, nsplit2, sp, sp2);
+}
+__global__ __launch_bounds__(64) void unbwt_wide_offsets2_kernel(const BwtStream* streams, const uint32_t* sp2_off, uint4* sp2, uint32_t* status) {
+  unbwt_wide_offsets2_body(streams, sp2_off, sp2, status);
+}
+__global__ __launch_bounds__(256) void unbwt_wide_offsets1_kernel(const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t nsplit2,
+                                                                  uint4* sp, const uint4* sp2, const uint32_t* status) {
+  unbwt_wide_offsets1_body(streams, sp2_off, nstreams, nsplit2, sp, sp2, status);
+}
+__global__ __launch_bounds__(256) void unbwt_wide_emit_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link,
+                                                              const uint4* sp, const uint32_t* status, uint8_t* out_all) {
+  unbwt_wide_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
 }
 
 __global__ __launch_bounds__(256) void une8_mark_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt,
@@ -396,6 +422,28 @@ hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, ui
   hipLaunchKernelGGL(unbwt_rank_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint32_t*)link, sp);
   hipLaunchKernelGGL(unbwt_offsets_kernel, dim3(nstreams), dim3(64), 0, st, streams, sp, status);
   hipLaunchKernelGGL(unbwt_emit_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint32_t*)link, (const uint4*)sp,
+                     (const uint32_t*)status, out_all);
+  return hipGetLastError();
+}
+
+// device/bwt_decode_wide_kernel.h: the eight stages for a batch of admitted wide streams, one after the other on `st`
+hipError_t launch_bwt_decode_wide(const uint8_t* in_all, const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t ntiles,
+                                  uint32_t nsplit, uint32_t nsplit2, uint32_t* hist, uint64_t* link, void* splitters, void* splitters2, uint32_t* status,
+                                  uint8_t* out_all, hipStream_t st) {
+  if (!nstreams) return hipSuccess;
+  if (nstreams > 65535u || !ntiles || !nsplit || !nsplit2) return hipErrorInvalidValue;
+  uint4* sp = (uint4*)splitters;
+  uint4* sp2 = (uint4*)splitters2;
+  const uint32_t spb = (nsplit + 255u) / 256u, spb2 = (nsplit2 + 255u) / 256u;
+  hipLaunchKernelGGL(unbwt_count_kernel, dim3(ntiles), dim3(64), 0, st, in_all, streams, nstreams, hist);
+  hipLaunchKernelGGL(unbwt_wide_scan_kernel, dim3(nstreams), dim3(256 * kBwtScanParts), 0, st, streams, hist);
+  hipLaunchKernelGGL(unbwt_wide_link_kernel, dim3(ntiles), dim3(64), 0, st, in_all, streams, nstreams, (const uint32_t*)hist, link);
+  hipLaunchKernelGGL(unbwt_wide_rank_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint64_t*)link, sp);
+  hipLaunchKernelGGL(unbwt_wide_rank2_kernel, dim3(spb2), dim3(256), 0, st, streams, sp2_off, nstreams, nsplit2, (const uint4*)sp, sp2);
+  hipLaunchKernelGGL(unbwt_wide_offsets2_kernel, dim3(nstreams), dim3(64), 0, st, streams, sp2_off, sp2, status);
+  hipLaunchKernelGGL(unbwt_wide_offsets1_kernel, dim3(spb2), dim3(256), 0, st, streams, sp2_off, nstreams, nsplit2, sp, (const uint4*)sp2,
+                     (const uint32_t*)status);
+  hipLaunchKernelGGL(unbwt_wide_emit_kernel, dim3(spb), dim3(256), 0, st, streams, nstreams, nsplit, (const uint64_t*)link, (const uint4*)sp,
                      (const uint32_t*)status, out_all);
   return hipGetLastError();
 }

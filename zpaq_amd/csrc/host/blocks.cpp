@@ -561,7 +561,7 @@ std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
 // args[0] is pm - 20; level 2's minimum match is read where two generated programs differ, then confirmed by the whole comparison.
 // kind: args[1] of the method -- 1 / 2 the LZ77 levels, 3 the BWT, 4 .. 7 the same (or nothing) behind E8E9.
-struct StreamProgram { int kind; U32 rb, min_match, mbits; };
+struct StreamProgram { int kind; U32 rb, min_match, mbits; bool wide = false; };   // wide: the BWT program at args[0] 5 .. 11
 bool unlz_generated(int a0, const std::string& body, std::vector<U8>& key) {
   try {
     int args[9];
@@ -595,19 +595,22 @@ int device_route_mode(const char* knob) {
   if (!v || !*v) return 2;
   return v[0] == '0' ? 0 : 1;
 }
-// The inverse BWT without E8E9 at args[0] <= 4 (pcomp_bwt(arg0, false): the byte rides in the list's word), recognised the same
-// way; ph and pm are both args[0] + 20.
+// The inverse BWT without E8E9 (pcomp_bwt(arg0, false)), recognised the same way; ph and pm are both args[0] + 20.  At
+// args[0] <= 4 the byte rides in the list's word (device/bwt_decode_kernel.h); at 5 .. 11 the entry is a full position and the
+// group is wide (device/bwt_decode_wide_kernel.h) -- whatever the size of its blocks.
 bool unbwt_program(const std::vector<U8>& key, StreamProgram& u) {
   if (key.size() < 3 || key[0] != key[1]) return false;
   const int a0 = (int)key[1] - 20;
-  if (a0 < 0 || a0 > 4) return false;
+  if (a0 < 0 || a0 > 11) return false;
   std::vector<U8> k;
   if (!unlz_generated(a0, ",3", k) || k != key) return false;
   u = StreamProgram{3, 0u, 0u, (U32)key[1]};
+  u.wide = a0 > 4;
   return true;
 }
 // The programs of the E8E9 methods -- the filter alone (",4": ph = pm = 0, the same program whatever args[0]), in front of LZ77
-// level 1 (",5") and level 2 (",6,mm"), in front of the BWT at args[0] <= 4 (",7") -- recognised the same way.
+// level 1 (",5") and level 2 (",6,mm"), in front of the BWT (",7"; wide at args[0] 5 .. 11, where the program filters through a
+// 5-byte window as it walks) -- recognised the same way.
 bool une8_program(const std::vector<U8>& key, StreamProgram& u) {
   if (key.size() < 3) return false;
   std::vector<U8> k1, k2;
@@ -619,8 +622,9 @@ bool une8_program(const std::vector<U8>& key, StreamProgram& u) {
   const int a0 = (int)key[1] - 20;
   if (a0 < 0 || a0 > 11) return false;
   if (key[0] == key[1]) {
-    if (a0 > 4 || !unlz_generated(a0, ",7", k1) || k1 != key) return false;
+    if (!unlz_generated(a0, ",7", k1) || k1 != key) return false;
     u = StreamProgram{7, 0u, 0u, (U32)key[1]};
+    u.wide = a0 > 4;
     return true;
   }
   if (key[0] != 0) return false;
@@ -773,7 +777,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
     // no route is forced.  One route: `how` is its knob (device_route_mode), `match` recognises a group's program, `pays` is its
     // rule for an unset knob, `decode` its engine call; its counter is stored only when the route is on.  Segments it declines
     // stay in their group and go on exactly as before.
-    auto route = [&](int how, bool (*match)(const std::vector<U8>&, StreamProgram&), bool (*pays)(U64, U64),
+    auto route = [&](int how, bool (*match)(const std::vector<U8>&, StreamProgram&), bool (*pays)(const StreamProgram&, U64, U64),
                      int (*decode)(const StreamProgram&, std::vector<StreamJob>&, std::string&), std::atomic<U32>& counter) {
       if (!how || !nprog || engine_device_count() <= 0) return;
       U32 taken = 0;
@@ -789,7 +793,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
           uj.push_back(StreamJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[i]});
           bytes += s.decoded.size() - skip;
         }
-        if (how != 1 && !pays(uj.size(), bytes)) continue;
+        if (how != 1 && !pays(u, uj.size(), bytes)) continue;
         std::string note;
         if (decode(u, uj, note) != 1) continue;
         std::vector<size_t> left;
@@ -804,18 +808,25 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
     };
     // The LZ77 inverses without E8E9 (device/lz77_decode_kernel.h: a wavefront per segment, not a lane): ZPAQ_AMD_DEVICE_UNLZ=0|1
     // forces the route off or on, unset follows lz_unlz_pays.
-    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ"), unlz_program, lz_unlz_pays,
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ"), unlz_program, [](const StreamProgram&, U64 segs, U64 bytes) { return lz_unlz_pays(segs, bytes); },
           [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_lz77_decode((U32)u.kind, u.rb, u.min_match, u.mbits, uj, note); },
           g_last_unlz_segments);
     // The inverse BWT without E8E9 likewise (device/bwt_decode_kernel.h: a counting sort per tile, the list ranked from every
-    // 256th node at once): ZPAQ_AMD_DEVICE_UNBWT=0|1 forces it off or on, unset follows bwt_unbwt_pays.
-    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNBWT"), unbwt_program, bwt_unbwt_pays,
-          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_bwt_decode(u.mbits, uj, note); }, g_last_unbwt_segments);
+    // 256th node at once): ZPAQ_AMD_DEVICE_UNBWT=0|1 forces it off or on, unset follows bwt_unbwt_pays -- for the program at
+    // args[0] 5 .. 11 (device/bwt_decode_wide_kernel.h) bwt_unbwt_wide_pays.  The counter counts the segments of either form.
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNBWT"), unbwt_program,
+          [](const StreamProgram& u, U64 segs, U64 bytes) { return u.wide ? bwt_unbwt_wide_pays(segs, bytes) : bwt_unbwt_pays(segs, bytes); },
+          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) {
+            return u.wide ? engine_bwt_decode_wide(u.mbits, false, uj, note) : engine_bwt_decode(u.mbits, uj, note);
+          }, g_last_unbwt_segments);
     // The E8E9 methods likewise: their stage's decoder, then the inverse filter over its output on the device
     // (device/e8e9_kernel.h: the scan is serial only along short chains).  ZPAQ_AMD_DEVICE_UNE8=0|1 forces it off or on, unset
     // follows e8_une8_pays.
-    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNE8"), une8_program, e8_une8_pays,
-          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) { return engine_e8e9_decode(u.kind, u.rb, u.min_match, u.mbits, uj, note); },
+    route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNE8"), une8_program,
+          [](const StreamProgram& u, U64 segs, U64 bytes) { return u.wide ? bwt_une8_wide_pays(segs, bytes) : e8_une8_pays(segs, bytes); },
+          [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) {
+            return u.wide ? engine_bwt_decode_wide(u.mbits, true, uj, note) : engine_e8e9_decode(u.kind, u.rb, u.min_match, u.mbits, uj, note);
+          },
           g_last_une8_segments);
     if (nprog && (force_dev || nprog >= 4 || prog_bytes >= (256u << 10)) && engine_device_count() > 0) {
       U32 taken = 0;
