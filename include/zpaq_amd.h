@@ -300,11 +300,34 @@ int zpq_suffix_array_device_wide(const uint8_t* in, uint32_t n, uint32_t* out);
 uint32_t zpq_last_wide_sort_blocks(void);
 uint32_t zpq_last_wide_sort_rounds(void);
 /* zpq_preprocess_block for one buffer with the sort by the wide sorter, for any method whose pre-processor sorts suffixes and
- * any n below 2^31: a BWT method's last column is made on the device, an LZ77 method is parsed by the host with the device's
- * array.  Byte for byte zpq_preprocess_block's stream; *len is always reported and nothing is written when cap is short
+ * any n below 2^31: a BWT method's last column is made on the device; an LZ77 method is parsed by the host with the device's
+ * array, or -- ZPAQ_AMD_DEVICE_PARSE_WIDE=1; unset: where the measured rule says so, DESIGN 4.5.9 -- on the device in pieces
+ * (device/lz77_wide_kernel.h), its codes written there as well as ZPAQ_AMD_DEVICE_CODES says.  Byte for byte
+ * zpq_preprocess_block's stream whichever path makes it; *len is always reported and nothing is written when cap is short
  * (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED for a method that does not sort suffixes, without a device, or when the device
  * declines; `data` is then as it came (an E8E9 method's filter is taken back on every failure). */
 int zpq_preprocess_block_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint8_t* out, size_t cap, size_t* len);
+/* The LZ77 parse of ONE buffer of any length below 2^31 on the device: E8E9 in place as the method says, the wide sort, then the
+ * search (a lane per position), the walk of pieces of 64 KiB from provisional starts (a wavefront each), the stitch that adopts
+ * a piece's list where the true walk meets it in an identical state, and the gather (device/lz77_wide_kernel.h).
+ * The list in zpq_lz77_tokens_host's layout, token for token the host's; *count is always reported and nothing is written when
+ * cap is short (ZPQ_E_OVERFLOW).  ZPQ_E_UNSUPPORTED with a note in zpq_last_error for a method whose LZ77 does not search a suffix
+ * array (or that is no LZ77), without a device, for input outside the range (min_match >= 1, lookahead <= 255, 1 <= checkbits
+ * <= 31, offset bits <= 7), or when the sort and the parse do not fit the device budget; `data` is as it came on every failure.
+ * ZPAQ_AMD_LZ_WIDE_PIECE=<bytes>, read per call, overrides the piece size (clamped to [64, 2^30], rounded up to a multiple of
+ * 64: tests).
+ * zpq_compress_blocks parses a wide LZ77 block this way with ZPAQ_AMD_DEVICE_PARSE_WIDE=1 (0: never; unset: where the measured
+ * rule says so, never below 2^24 bytes; ZPAQ_AMD_DEVICE_PARSE=0 wins: sort only); archives are identical whichever path parses
+ * and codes.  zpq_last_wide_parse_blocks: the blocks of this process's last zpq_compress_blocks call that were parsed there.
+ * zpq_last_wide_parse_pieces, of this process's last wide parse: pieces, pieces adopted whole, pieces re-joined after a re-walk,
+ * pieces that contributed only re-walked tokens or nothing (the four add up).
+ * zpq_wide_stage_bytes: what a wide call for a block of n bytes holds on the device, as its budget check sums it -- out2[0] the
+ * sort alone, out2[1] the sort with the parse and the coder's arrays (equal for a BWT method).  A block whose second sum exceeds
+ * the budget but whose first does not is sorted there and parsed by the host.  Needs no device. */
+int zpq_lz77_parse_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint32_t* tokens4, size_t cap, size_t* count);
+uint32_t zpq_last_wide_parse_blocks(void);
+void zpq_last_wide_parse_pieces(uint32_t out4[4]);
+int zpq_wide_stage_bytes(const char* xmethod, uint32_t n, uint64_t out2[2]);
 int zpq_suffix_array_host(const uint8_t* in, uint32_t n, uint32_t* out);      /* the host's sorter (SA-IS), one buffer */
 /* compressBlock's level->method expansion (libzpaq.cpp:7579-7691), including
  * level-5 period detection on the data.  Writes a NUL-terminated "x..." /

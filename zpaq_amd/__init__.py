@@ -115,6 +115,12 @@ def lib():
     L.zpq_last_wide_sort_blocks.argtypes = []
     L.zpq_last_wide_sort_rounds.restype = C.c_uint32
     L.zpq_last_wide_sort_rounds.argtypes = []
+    L.zpq_lz77_parse_device_wide.argtypes = [C.c_char_p, _u8p, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.zpq_last_wide_parse_blocks.restype = C.c_uint32
+    L.zpq_last_wide_parse_blocks.argtypes = []
+    L.zpq_last_wide_parse_pieces.restype = None
+    L.zpq_last_wide_parse_pieces.argtypes = [C.POINTER(C.c_uint32)]
+    L.zpq_wide_stage_bytes.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.zpq_last_fragment_rounds.restype = C.c_uint32
     L.zpq_last_fragment_rounds.argtypes = []
     L.zpq_fragment_analyze.restype = C.c_uint32
@@ -347,6 +353,39 @@ def preprocess_block_device_wide(xmethod: str, data, cap: int, guard: int = 0, f
     ol = C.c_size_t(0)
     rc = lib().zpq_preprocess_block_device_wide(xmethod.encode(), _p(src), n, _p(out), int(cap), C.byref(ol))
     return rc, out[:int(cap) + guard].tobytes(), int(ol.value)
+
+
+def lz77_parse_device_wide(xmethod: str, data, cap: int, spare: int = 0, fill: int = 0):
+    """zpq_lz77_parse_device_wide: the LZ77 parse of one buffer of any length below 2^31 on the device, behind the wide sorter.
+    `data` (a writable uint8 array, or bytes that are copied) is E8E9-filtered in place where the method says so.  `spare` token
+    slots of `fill` words lie behind the `cap` slots of the list.  Returns (return code, the buffer -- 4 x (cap + spare) words of
+    uint32, as the call left it --, count)."""
+    a = data if isinstance(data, np.ndarray) else _arr(data)
+    n = int(a.size)
+    src = a if n else np.zeros(1, np.uint8)
+    out = np.full(max(4 * (int(cap) + spare), 4), fill, np.uint32)
+    cnt = C.c_size_t(0)
+    rc = lib().zpq_lz77_parse_device_wide(xmethod.encode(), _p(src), n, out.ctypes.data_as(C.POINTER(C.c_uint32)), int(cap), C.byref(cnt))
+    return rc, out[:4 * (int(cap) + spare)], int(cnt.value)
+
+
+def last_wide_parse_blocks() -> int:
+    """Blocks of the last compress_blocks call whose LZ77 parse ran on the device behind the wide sorter (ZPAQ_AMD_DEVICE_PARSE_WIDE)."""
+    return int(lib().zpq_last_wide_parse_blocks())
+
+
+def last_wide_parse_pieces() -> Tuple[int, int, int, int]:
+    """Of this process's last wide parse: pieces, adopted whole, re-joined after a re-walk, own tokens only or nothing."""
+    out = (C.c_uint32 * 4)()
+    lib().zpq_last_wide_parse_pieces(out)
+    return tuple(int(x) for x in out)
+
+
+def wide_stage_bytes(xmethod: str, n: int) -> Tuple[int, int]:
+    """zpq_wide_stage_bytes: what a wide call for n bytes holds on the device -- (the sort alone, the sort with parse and codes)."""
+    out = (C.c_uint64 * 2)()
+    _check(lib().zpq_wide_stage_bytes(xmethod.encode(), int(n), out))
+    return int(out[0]), int(out[1])
 
 
 def last_wide_sort_blocks() -> int:

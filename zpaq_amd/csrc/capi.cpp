@@ -418,9 +418,65 @@ int zpq_suffix_array_device_wide(const uint8_t* in, uint32_t n, uint32_t* out) {
 uint32_t zpq_last_wide_sort_blocks(void) { return last_wide_sort_blocks(); }
 uint32_t zpq_last_wide_sort_rounds(void) { return engine_last_wide_sort_rounds(); }
 
+uint32_t zpq_last_wide_parse_blocks(void) { return last_wide_parse_blocks(); }
+void zpq_last_wide_parse_pieces(uint32_t out4[4]) { if (out4) engine_last_wide_parse_pieces(out4); }
+
+// What a wide call holds on the device: out2[0] the sort alone, out2[1] the sort with the parse and the coder's arrays
+int zpq_wide_stage_bytes(const char* xmethod, uint32_t n, uint64_t out2[2]) {
+  ZPQ_TRY
+  if (!xmethod || !out2) fail(ZPQ_E_ARG, "null argument");
+  int args[9];
+  (void)make_config(xmethod, args);
+  if (!preprocess_needs_suffix_array(args)) fail(ZPQ_E_UNSUPPORTED, "the method's pre-processor does not sort suffixes");
+  if (n >= (1u << 31)) fail(ZPQ_E_UNSUPPORTED, "block outside the wide sorter's range");
+  U64 sums[2];
+  engine_wide_stage_bytes(sort_job(nullptr, n, args), sums);
+  out2[0] = sums[0];
+  out2[1] = sums[1];
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
+// E8E9 applied in place for the length of a stage call: taken back on every failure exit, as in zpq_preprocess_blocks_device
+namespace {
+struct Unfilter {
+  uint8_t* data; uint32_t n; bool done = false, keep = false;
+  ~Unfilter() { if (done && !keep) e8e9_inverse(data, n); }
+};
+}  // namespace
+
+// The wide stage's parse on its own: E8E9 as the method says, the wide sort, the parse in pieces (device/lz77_wide_kernel.h).
+// The list in zpq_lz77_tokens_host's layout; *count always, nothing is written when cap is short.
+int zpq_lz77_parse_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint32_t* tokens4, size_t cap, size_t* count) {
+  ZPQ_TRY
+  if (!xmethod || (!data && n) || !count || (!tokens4 && cap)) fail(ZPQ_E_ARG, "null argument");
+  *count = 0;
+  int args[9];
+  (void)make_config(xmethod, args);
+  const int level = args[1] & 3;
+  if (!preprocess_needs_suffix_array(args) || level < 1 || level > 2)
+    fail(ZPQ_E_UNSUPPORTED, "wide parse on the device unavailable: the method's LZ77 does not search a suffix array");
+  if (n >= (1u << 31)) fail(ZPQ_E_UNSUPPORTED, "wide parse on the device unavailable: block outside the wide sorter's range");
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "wide parse on the device unavailable: no device");
+  if (n == 0) return ZPQ_OK;
+  Unfilter guard{data, n};
+  if (args[1] > 4) { e8e9_forward(data, n); guard.done = true; }
+  SortOut so;
+  std::string note;
+  if (!engine_sort_wide(sort_job(data, n, args), so, note, false, 0, true)) fail(ZPQ_E_UNSUPPORTED, "wide parse on the device unavailable: " + note);
+  if (!so.parsed) fail(ZPQ_E_UNSUPPORTED, "wide parse on the device unavailable: " + note);
+  *count = so.toks.size();
+  if (so.toks.size() > cap) fail(ZPQ_E_OVERFLOW, "token buffer too small");
+  if (!so.toks.empty()) memcpy(tokens4, so.toks.data(), so.toks.size() * sizeof(LzToken));
+  guard.keep = true;
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+
 // What zpq_preprocess_block makes of one buffer, the sort by the wide sorter: a BWT method's last column is emitted on the
-// device, an LZ77 method that sorts suffixes is parsed by the host with the device's array.  E8E9 is applied in place and taken
-// back on every failure exit, as in zpq_preprocess_blocks_device.
+// device; an LZ77 method that sorts suffixes is parsed by the host with the device's array, or -- ZPAQ_AMD_DEVICE_PARSE_WIDE=1, or
+// unset and lz_wide_parse_pays -- on the device in pieces, its codes written there too as ZPAQ_AMD_DEVICE_CODES says.  E8E9 is
+// applied in place and taken back on every failure exit, as in zpq_preprocess_blocks_device.
 int zpq_preprocess_block_device_wide(const char* xmethod, uint8_t* data, uint32_t n, uint8_t* out, size_t cap, size_t* len) {
   ZPQ_TRY
   if (!xmethod || (!data && n) || !len) fail(ZPQ_E_ARG, "null argument");
@@ -429,18 +485,20 @@ int zpq_preprocess_block_device_wide(const char* xmethod, uint8_t* data, uint32_
   if (!preprocess_needs_suffix_array(args)) fail(ZPQ_E_UNSUPPORTED, "the method's pre-processor does not sort suffixes");
   if (n >= (1u << 31)) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: block outside the wide sorter's range");
   if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: no device");
-  struct Unfilter {
-    uint8_t* data; uint32_t n; bool done = false, keep = false;
-    ~Unfilter() { if (done && !keep) e8e9_inverse(data, n); }
-  } guard{data, n};
+  Unfilter guard{data, n};
   if (args[1] > 4) { e8e9_forward(data, n); guard.done = true; }
   std::vector<U8> pre;
   if (n == 0) (void)preprocess_block(data, 0, args, pre, nullptr, true);
   else {
     SortOut so;
     std::string note;
-    if (!engine_sort_wide(sort_job(data, n, args), so, note, false)) fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
+    const int mode = device_parse_wide_mode();
+    const bool parse_there = (args[1] & 3) != 3 && (mode == 1 || (mode == 2 && n >= (1u << 24) && lz_wide_parse_pays(n)));
+    if (!engine_sort_wide(sort_job(data, n, args), so, note, false, parse_there ? device_codes_mode() : -1))
+      fail(ZPQ_E_UNSUPPORTED, "pre-processing on the device unavailable: " + note);
     if ((args[1] & 3) == 3) pre.swap(so.bwt);
+    else if (so.parsed && so.coded) pre.swap(so.codes);
+    else if (so.parsed) lz77_serialize(data, n, args, so.toks.data(), so.toks.size(), pre);
     else (void)preprocess_block(data, n, args, pre, so.sa.data(), true);
   }
   *len = pre.size();                                      // (the size is reported also when the buffer is too small)

@@ -78,7 +78,7 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
 // codes: LZBuffer's codes are written on the device as well (device/lz77_codes_kernel.h) -- a block of kind 1 / 2 then comes back
 // as its finished stream in SortOut::codes (coded = true) and its list of matches is not downloaded.
 struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0, rb = 0; };   // (min_match2, ht_bits: hash_job; rb: the coder)
-struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; std::vector<U32> sa; };   // (sa: engine_sort_wide)
+struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; std::vector<U32> sa; bool parsed = false; };   // (sa, parsed: engine_sort_wide)
 // codes: 0 the lists come back; 1 the streams; 2 the streams when that pays -- decided per batch once the sizes are known, by
 // lz_codes_pay below (DESIGN 4.5.2 has the measurement behind it)
 bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOut>& out, std::string& note, int codes = 0);
@@ -97,10 +97,29 @@ inline SortJob sort_job(const U8* data, U32 n, const int args[9]) {
 }
 // ONE block of any length below 2^31 through the wide sorter (device/sa_wide_kernel.h, DESIGN 4.5.7: no block id in the key, two
 // rank fields of up to 31 bits).  A block of kind 3 comes back as its BWT stream in out.bwt (n + 5 bytes, emitted on the device
-// from the ranks) unless want_sa; every other block, and every block with want_sa, as its suffix array in out.sa -- the host
-// parses or transforms with it.  false + note when the device declines (the block, its array or column and 32 bytes of workspace
-// per byte within the engine's budget): nothing was launched, the host sorts.
-bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa);
+// from the ranks) unless want_sa.  A block of kind 1 / 2 with parse_codes >= 0 and not want_sa is parsed there as well, in pieces
+// (device/lz77_wide_kernel.h, DESIGN 4.5.9: n < 2^31, min_match >= 1, lookahead <= 255, 1 <= checkbits <= 31, rb <= 7) and comes
+// back with out.parsed set, as its list of matches in out.toks or -- parse_codes 1, or 2 and lz_codes_pay -- as its stream in
+// out.codes (coded = true), exactly as a batch's blocks do.  Every other block, every block with want_sa, and a block whose sort
+// fits the budget but whose parse does not, or whose parse failed (an overflowed list, one the coder's checks refuse, a launch
+// error: the note says), comes back as its suffix array in out.sa -- the host parses or transforms with it.  false + note when
+// the device declines (the block, its array or column and 32 bytes of workspace per byte within the engine's budget): nothing was
+// launched, the host sorts.
+// parse_or_nothing: the caller wants the parse and has no use for the array -- where the parse cannot run (the range, the budget)
+// the call declines before anything is launched.
+bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa, int parse_codes = -1, bool parse_or_nothing = false);
+// What such a call holds on the device -- the sums its budget check makes: out[0] the sort alone, out[1] the sort with the parse
+// and the coder's arrays behind it (equal for a block that is not parsed there).  Needs no device.  ZPAQ_AMD_LZ_WIDE_PIECE=<bytes>,
+// read per call, overrides the piece size (kLzWidePiece; clamped to [64, 2^30], rounded up to a multiple of 64: tests).
+void engine_wide_stage_bytes(const SortJob& job, U64 out[2]);
+// pieces of this process's last wide parse: all, adopted whole, re-joined after a re-walk, own tokens only or nothing
+void engine_last_wide_parse_pieces(U32 out[4]);
+// Whether the parse of a wide LZ77 block runs on the device when ZPAQ_AMD_DEVICE_PARSE_WIDE is unset.  The rule is that of
+// sa_wide_pays, fixed before the measurement: from the smallest measured block size at which the device parse beat the host's
+// in all three alternations on every kind of data, never below 2^24 bytes; off, behind the knob only, if some kind loses at every
+// size.  Zeros do: 381 against 105 ms at 16 MiB + 4096, 1511 against 476 ms at 64 MiB - 4096 (the search compares a run's 49 152
+// bytes at every position) -- while text, records and random bytes are parsed 14 to 55 times faster (DESIGN 4.5.9 has the table).
+inline bool lz_wide_parse_pays(U64 /*n*/) { return false; }
 U32 engine_last_wide_sort_rounds();    // doubling rounds of this process's last engine_sort_wide call that sorted
 // Whether a sorting block of n bytes takes the wide route when ZPAQ_AMD_DEVICE_SORT_WIDE is unset.  The rule, fixed before the
 // measurement: from the smallest measured block size at which the route beat the host's sorter in all three alternations on

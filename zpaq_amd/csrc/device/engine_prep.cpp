@@ -3,6 +3,7 @@
 // its batch holds on the device against the engine's budget, stages its inputs, launches, and delivers or declines.
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <cstdlib>
 
 #include "engine_internal.hpp"
@@ -101,53 +102,6 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
   }
   HIP_CHECK(hipStreamSynchronize(e.stream));
   note = "device, " + std::to_string(rounds) + " doubling rounds";
-  return true;
-}
-
-// The wide sorter for one block (device/sa_wide_kernel.h): the block up, the doubling rounds, then either the BWT's last column
-// straight from the ranks (kind 3 unless the caller wants the array: n + 5 bytes come back) or the array (4 n bytes; the host
-// parses or transforms with it).  Everything the call holds on the device is summed against the budget before anything is
-// launched.  Blocks go one after another on the engine's stream.
-static std::atomic<U32> g_last_wide_rounds{0};
-U32 engine_last_wide_sort_rounds() { return g_last_wide_rounds.load(std::memory_order_relaxed); }
-
-bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa) {
-  out = SortOut();
-  const uint64_t n = job.n;
-  if (!n) return true;
-  if (n >= (1ull << 31)) { note = "block outside the wide sorter's range"; return false; }
-  if (job.kind > 3) { note = "unknown pre-processor kind"; return false; }
-  const bool bwt = job.kind == 3 && !want_sa;
-  EngineCall call;
-  Engine& e = call.e;
-  const size_t ws = sa_wide_workspace_bytes(n);
-  const uint64_t in_bytes = align_up(n, 256);
-  const uint64_t out_bytes = (bwt ? 256 + n + 1 : 4 * n) + 256;       // (BWT: the index word in front of the column)
-  if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "suffix sort workspace exceeds the device budget"; return false; }
-  e.io_in.ensure(in_bytes + 64);
-  e.io_out.ensure(out_bytes);
-  e.arena.ensure(ws);
-  HIP_CHECK(hipMemcpyAsync(e.io_in.p, job.data, n, hipMemcpyHostToDevice, e.stream));
-  uint8_t* const ob = (uint8_t*)e.io_out.p;
-  uint32_t rounds = 0;
-  const uint32_t* d_rank = nullptr;
-  hipError_t rc = build_suffix_array_wide((const uint8_t*)e.io_in.p, (uint32_t)n, bwt ? nullptr : (uint32_t*)ob, e.arena.p, e.arena.cap, e.stream, &rounds, &d_rank);
-  if (rc == hipSuccess && bwt) rc = launch_bwt_wide((const uint8_t*)e.io_in.p, d_rank, (uint32_t)n, ob + 256, (uint32_t*)ob, e.stream);
-  if (launch_failed(rc, "device wide suffix sort failed: ", note)) return false;
-  if (bwt) {
-    uint32_t idx = 0;
-    out.bwt.resize((size_t)n + 5);
-    HIP_CHECK(hipMemcpyAsync(out.bwt.data(), ob + 256, (size_t)n + 1, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipMemcpyAsync(&idx, ob, 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    for (int k = 0; k < 4; ++k) { out.bwt[(size_t)n + 1 + k] = (U8)idx; idx >>= 8; }
-  } else {
-    out.sa.resize((size_t)n);
-    HIP_CHECK(hipMemcpyAsync(out.sa.data(), ob, 4 * n, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-  }
-  g_last_wide_rounds.store(rounds, std::memory_order_relaxed);
-  note = "device (wide), " + std::to_string(rounds) + " doubling rounds";
   return true;
 }
 
@@ -257,6 +211,151 @@ static bool parse_results(Engine& e, const std::vector<LzBlock>& blk, uint64_t t
     if (cnt[i]) HIP_CHECK(hipMemcpyAsync(out[i].toks.data(), a.ob + a.o_tok + 16 * B.tok_off, 16ull * cnt[i], hipMemcpyDeviceToHost, e.stream));
   }
   HIP_CHECK(hipStreamSynchronize(e.stream));
+  return true;
+}
+
+// The wide sorter for one block (device/sa_wide_kernel.h): the block up, the doubling rounds, then one of three ends.  Kind 3
+// unless the caller wants the array: the BWT's last column straight from the ranks (n + 5 bytes come back).  Kind 1 / 2 with
+// parse_codes >= 0: the parse in pieces (device/lz77_wide_kernel.h) and, as device_codes_mode says, LZBuffer's codes over a
+// one-entry block table -- the list of matches or the stream comes back.  Else the array (4 n bytes; the host parses or
+// transforms with it).  Everything the call holds on the device is summed against the budget before anything is launched.
+// Blocks go one after another on the engine's stream.
+static std::atomic<U32> g_last_wide_rounds{0};
+U32 engine_last_wide_sort_rounds() { return g_last_wide_rounds.load(std::memory_order_relaxed); }
+static std::atomic<U32> g_last_wide_pieces[4];
+void engine_last_wide_parse_pieces(U32 out[4]) { for (int k = 0; k < 4; ++k) out[k] = g_last_wide_pieces[k].load(std::memory_order_relaxed); }
+
+static uint32_t wide_piece() {
+  U64 piece = kLzWidePiece;
+  if (const char* v = getenv("ZPAQ_AMD_LZ_WIDE_PIECE")) { const long long x = atoll(v); if (x > 0) piece = (U64)x; }
+  return lz_wide_piece_clamp(piece);
+}
+static bool wide_parse_in_range(const SortJob& j) {
+  return (j.kind == 1 || j.kind == 2) && j.n < (1u << 31) && j.min_match >= 1 && j.lookahead <= 255 && j.checkbits >= 1 && j.checkbits <= 31 && j.rb <= 7;
+}
+
+// What a wide call holds on the device.  io_in: the block.  The arena buffer: the sorter's workspace (the ranks stay there for the
+// search).  io_out: the array -- or the BWT's index word and column -- and, with the parse behind it, decisions (16 B per
+// position), the final list, the pieces' slots, records and adoptions, the counts, the one-entry block table, the coder's arrays.
+struct WidePlan {
+  size_t ws = 0;
+  uint64_t in_bytes = 0, sort_out = 0, parse_out = 0;
+  LzWideParams W{};
+  uint32_t tok_cap = 0;
+  uint64_t o_res = 0, o_tok = 0, o_prov = 0, o_pieces = 0, o_adopt = 0, o_result = 0, o_blk = 0;
+  CodesLayout cl;
+  uint64_t held(bool parse) const { return ws + in_bytes + (parse ? parse_out : sort_out) + (1u << 20); }
+};
+static WidePlan wide_plan(const SortJob& job, bool bwt, uint32_t piece) {
+  WidePlan P;
+  const uint64_t n = job.n;
+  P.ws = sa_wide_workspace_bytes(n);
+  P.in_bytes = align_up(n, 256);
+  P.sort_out = (bwt ? 256 + n + 1 : 4 * n) + 256;                      // (BWT: the index word in front of the column)
+  P.parse_out = P.sort_out;
+  if (bwt || !wide_parse_in_range(job)) return P;
+  P.W.n = job.n;
+  P.W.piece = piece;
+  P.W.npieces = (uint32_t)((n + piece - 1) / piece);
+  P.W.slot_cap = lz_wide_slot_cap(piece, job.min_match);
+  P.tok_cap = job.n / job.min_match + 2;
+  Carve cv;
+  cv.take(4 * n);
+  P.o_res = cv.take(16 * n);
+  P.o_tok = cv.take(16ull * P.tok_cap);
+  P.o_prov = cv.take(16ull * P.W.npieces * P.W.slot_cap);
+  P.o_pieces = cv.take(sizeof(LzWidePiece) * (uint64_t)P.W.npieces);
+  P.o_adopt = cv.take(sizeof(LzWideAdopt) * (uint64_t)P.W.npieces);
+  P.o_result = cv.take(sizeof(LzWideResult));
+  P.o_blk = cv.take(sizeof(LzBlock));
+  P.cl = codes_layout(cv, 1, (uint64_t)P.tok_cap + 1);
+  P.parse_out = P.cl.end + 256;
+  return P;
+}
+
+void engine_wide_stage_bytes(const SortJob& job, U64 out[2]) {
+  out[0] = out[1] = 0;
+  if (!job.n) return;
+  const WidePlan P = wide_plan(job, job.kind == 3, wide_piece());
+  out[0] = P.held(false);
+  out[1] = P.held(true);
+}
+
+// The parse behind the sort that has just run on e.stream (the array at the front of io_out, the ranks at d_rank).  false + note:
+// a list overflowed, the coder refused it, a launch failed -- the array is still where it was.
+static bool parse_wide(Engine& e, const SortJob& job, WidePlan& P, const uint32_t* d_rank, int codes, SortOut& out, std::string& note) {
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  std::vector<LzBlock> blk(1, lz_block(0, job.n, job.kind, job.min_match, job.rb, 0, P.tok_cap));
+  blk[0].lookahead = job.lookahead; blk[0].bucket = job.bucket; blk[0].checkbits = job.checkbits;
+  HIP_CHECK(hipMemcpyAsync(ob + P.o_blk, blk.data(), sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
+  HIP_CHECK(hipMemsetAsync(ob + P.o_result, 0, sizeof(LzWideResult), e.stream));
+  if (codes) { codes_bind(P.cl, ob); HIP_CHECK(hipMemsetAsync(P.cl.c.sizes, 0, 4 * 2, e.stream)); }
+  LzTok* const d_toks = (LzTok*)(ob + P.o_tok);
+  LzWideResult* const d_result = (LzWideResult*)(ob + P.o_result);
+  static_assert(offsetof(LzWideResult, count) == 0, "the coder reads the list's length as counts[0]");
+  hipError_t rc = launch_lz77_wide((const uint8_t*)e.io_in.p, (const uint32_t*)ob, d_rank, (const LzBlock*)(ob + P.o_blk), P.W, P.tok_cap, ob + P.o_res,
+                                   (LzTok*)(ob + P.o_prov), (LzWidePiece*)(ob + P.o_pieces), (LzWideAdopt*)(ob + P.o_adopt), d_toks, d_result, e.stream);
+  if (rc == hipSuccess && codes) rc = launch_lz77_code_lengths((const LzBlock*)(ob + P.o_blk), 1, d_toks, (const uint32_t*)d_result, P.cl.c, e.stream);
+  if (launch_failed(rc, "device wide parse failed: ", note)) return false;
+  LzWideResult r;
+  HIP_CHECK(hipMemcpyAsync(&r, d_result, sizeof r, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (r.overflow || r.count > P.tok_cap || r.pieces != P.W.npieces) { note = "LZ77 token list overflowed"; return false; }
+  std::vector<SortOut> outs(1);
+  bool coded = false;
+  if (!parse_results(e, blk, job.n, codes, P.cl, ParseArrays{ob, P.o_tok, P.o_result, P.o_blk}, ob + P.o_res, outs, note, &coded)) return false;
+  out = std::move(outs[0]);
+  out.parsed = true;
+  g_last_wide_pieces[0].store(r.pieces, std::memory_order_relaxed);
+  for (int k = 0; k < 3; ++k) g_last_wide_pieces[1 + k].store(r.how[k], std::memory_order_relaxed);
+  return true;
+}
+
+bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool want_sa, int parse_codes, bool parse_or_nothing) {
+  out = SortOut();
+  const uint64_t n = job.n;
+  if (!n) return true;
+  if (n >= (1ull << 31)) { note = "block outside the wide sorter's range"; return false; }
+  if (job.kind > 3) { note = "unknown pre-processor kind"; return false; }
+  const bool bwt = job.kind == 3 && !want_sa;
+  bool parse = !want_sa && parse_codes >= 0 && (job.kind == 1 || job.kind == 2);
+  std::string why;                                              // why the parse did not run here although it was asked for
+  if (parse && !wide_parse_in_range(job)) { parse = false; why = "LZ77 parameters outside the device parser's range"; }
+  EngineCall call;
+  Engine& e = call.e;
+  WidePlan P = wide_plan(job, bwt, wide_piece());
+  if (parse && P.held(true) > e.budget) { parse = false; why = "sort + parse workspace exceeds the device budget"; }
+  if (parse_or_nothing && !parse) { note = why.empty() ? "the block is not one the device parses" : why; return false; }   // (nothing was launched)
+  if (P.held(false) > e.budget) { note = "suffix sort workspace exceeds the device budget"; return false; }
+  e.io_in.ensure(P.in_bytes + 64);
+  e.io_out.ensure(parse ? P.parse_out : P.sort_out);
+  e.arena.ensure(P.ws);
+  HIP_CHECK(hipMemcpyAsync(e.io_in.p, job.data, n, hipMemcpyHostToDevice, e.stream));
+  uint8_t* const ob = (uint8_t*)e.io_out.p;
+  uint32_t rounds = 0;
+  const uint32_t* d_rank = nullptr;
+  hipError_t rc = build_suffix_array_wide((const uint8_t*)e.io_in.p, (uint32_t)n, bwt ? nullptr : (uint32_t*)ob, e.arena.p, e.arena.cap, e.stream, &rounds, &d_rank);
+  if (rc == hipSuccess && bwt) rc = launch_bwt_wide((const uint8_t*)e.io_in.p, d_rank, (uint32_t)n, ob + 256, (uint32_t*)ob, e.stream);
+  if (launch_failed(rc, "device wide suffix sort failed: ", note)) return false;
+  g_last_wide_rounds.store(rounds, std::memory_order_relaxed);
+  note = "device (wide), " + std::to_string(rounds) + " doubling rounds";
+  if (parse) {
+    if (parse_wide(e, job, P, d_rank, parse_codes, out, why)) { note += out.coded ? ", parsed and coded there" : ", parsed there"; return true; }
+    out = SortOut();                                            // (the array is still at the front of io_out: the host parses with it)
+  }
+  if (!why.empty()) note += "; " + why;
+  if (bwt) {
+    uint32_t idx = 0;
+    out.bwt.resize((size_t)n + 5);
+    HIP_CHECK(hipMemcpyAsync(out.bwt.data(), ob + 256, (size_t)n + 1, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipMemcpyAsync(&idx, ob, 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    for (int k = 0; k < 4; ++k) { out.bwt[(size_t)n + 1 + k] = (U8)idx; idx >>= 8; }
+  } else {
+    out.sa.resize((size_t)n);
+    HIP_CHECK(hipMemcpyAsync(out.sa.data(), ob, 4 * n, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+  }
   return true;
 }
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "layout.h"
+#include "lz77_wide_layout.h"
 
 namespace zpq {
 // what the sorter leaves in its workspace besides the arrays: rank[i] - 1 = position of suffix i in its block's suffix array (the
@@ -36,6 +37,13 @@ hipError_t launch_bwt_wide(const uint8_t* d_in, const uint32_t* d_rank, uint32_t
 hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_all, const SaSideArrays& side, const LzBlock* blocks, uint32_t nblocks,
                                      uint64_t total, bool any_lz, bool any_bwt, void* res, LzTok* toks, uint32_t* counts, uint8_t* bwt_out,
                                      uint32_t* bwt_idx, hipStream_t st, const LzCodes* codes = nullptr);
+// The LZ77 parse of the ONE block build_suffix_array_wide has just sorted (device/lz77_wide_kernel.h): the search (16 bytes of
+// decisions per position in `res`), the walk of W.npieces pieces of W.piece positions from provisional starts (W.slot_cap token
+// slots each in `prov`, {count, exit state} in `pieces`), the stitch (one wavefront: what it adopts of each piece in `adopt`, its
+// own tokens in `toks`, the counts in `out`) and the gather of the adopted tokens into toks[0 .. tok_cap).  blocks: the one-entry
+// table with the search parameters.  out->count is the list's length (more than tok_cap: incomplete) -- the coder's counts[0].
+hipError_t launch_lz77_wide(const uint8_t* d_in, const uint32_t* d_sa, const uint32_t* d_rank, const LzBlock* blocks, LzWideParams W, uint32_t tok_cap,
+                            void* res, LzTok* prov, LzWidePiece* pieces, LzWideAdopt* adopt, LzTok* toks, LzWideResult* out, hipStream_t st);
 // The LZ77 parse through LZBuffer's hash table for a batch (device/lz77_hash_kernel.h): keys, one radix sort, the index of slot
 // prefixes, the search (16 bytes of decisions per element in `res`), then lz77_walk_kernel as behind the sort.  The caller fills
 // blocks[b].ht_bits / min_match2 / ins_end / nkeys / key_off / idx_bits / idx_off; nkeys, nidx: the sums of the blocks' keys and

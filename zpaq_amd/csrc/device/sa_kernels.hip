@@ -30,6 +30,7 @@
 #include "lz77_decode_kernel.h"
 #include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
+#include "lz77_wide_kernel.h"
 #include "sa_kernel.h"
 #include "sa_kernels.h"
 #include "sa_wide_kernel.h"
@@ -75,6 +76,20 @@ __global__ __launch_bounds__(256) void lz77_search_kernel(const uint8_t* in_all,
 }
 __global__ __launch_bounds__(64) void lz77_walk_kernel(const LzBlock* blocks, const uint4* res, LzTok* toks, uint32_t* counts) {
   lz77_walk_body(blocks, res, toks, counts);
+}
+// device/lz77_wide_kernel.h: the parse of one block of any length below 2^31 in pieces
+__global__ __launch_bounds__(256) void lz77_wide_search_kernel(const uint8_t* in, const uint32_t* sa, const uint32_t* rank, const LzBlock* blocks, uint4* res) {
+  lz77_wide_search_body(in, sa, rank, blocks, res);
+}
+__global__ __launch_bounds__(64) void lz77_wide_walk_kernel(LzWideParams W, const uint4* res, LzTok* prov, LzWidePiece* pieces) {
+  lz77_wide_walk_body(W, res, prov, pieces);
+}
+__global__ __launch_bounds__(64) void lz77_wide_stitch_kernel(LzWideParams W, const uint4* res, const LzTok* prov, const LzWidePiece* pieces, LzTok* toks,
+                                                              uint32_t tok_cap, LzWideAdopt* adopt, LzWideResult* out) {
+  lz77_wide_stitch_body(W, res, prov, pieces, toks, tok_cap, adopt, out);
+}
+__global__ __launch_bounds__(256) void lz77_wide_gather_kernel(LzWideParams W, const LzTok* prov, const LzWideAdopt* adopt, LzTok* toks, uint32_t tok_cap) {
+  lz77_wide_gather_body(W, prov, adopt, toks, tok_cap);
 }
 __global__ __launch_bounds__(256) void bwt_emit_kernel(const uint8_t* in_all, const uint32_t* sa_all, const uint16_t* blk, const LzBlock* blocks,
                                                        uint64_t total, uint8_t* out_all, uint32_t* idx) {
@@ -321,6 +336,21 @@ hipError_t launch_sort_preprocessors(const uint8_t* in_all, const uint32_t* sa_a
   }
   if (any_bwt)
     hipLaunchKernelGGL(bwt_emit_kernel, dim3(g), dim3(256), 0, st, in_all, sa_all, (const uint16_t*)side.blk, blocks, total, bwt_out, bwt_idx);
+  return hipGetLastError();
+}
+
+// device/lz77_wide_kernel.h behind build_suffix_array_wide: search, piece walk, stitch, gather.  blocks: the one-entry table (off 0,
+// tok_off 0, tok_cap slots at toks); W.n = blocks[0].n, W.npieces pieces of W.piece positions with W.slot_cap slots each at prov.
+hipError_t launch_lz77_wide(const uint8_t* d_in, const uint32_t* d_sa, const uint32_t* d_rank, const LzBlock* blocks, LzWideParams W, uint32_t tok_cap,
+                            void* res, LzTok* prov, LzWidePiece* pieces, LzWideAdopt* adopt, LzTok* toks, LzWideResult* out, hipStream_t st) {
+  if (!W.n) return hipSuccess;
+  if (W.n >= (1u << 31) || W.piece < 64u || W.piece % 64u || W.npieces != (uint32_t)(((uint64_t)W.n + W.piece - 1u) / W.piece) || !W.slot_cap)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lz77_wide_search_kernel, dim3(grid_for(W.n)), dim3(256), 0, st, d_in, d_sa, d_rank, blocks, (uint4*)res);
+  hipLaunchKernelGGL(lz77_wide_walk_kernel, dim3(W.npieces), dim3(64), 0, st, W, (const uint4*)res, prov, pieces);
+  hipLaunchKernelGGL(lz77_wide_stitch_kernel, dim3(1), dim3(64), 0, st, W, (const uint4*)res, (const LzTok*)prov, (const LzWidePiece*)pieces, toks, tok_cap,
+                     adopt, out);
+  hipLaunchKernelGGL(lz77_wide_gather_kernel, dim3(W.npieces), dim3(256), 0, st, W, (const LzTok*)prov, (const LzWideAdopt*)adopt, toks, tok_cap);
   return hipGetLastError();
 }
 

@@ -195,6 +195,13 @@ void parallel_blocks(size_t n, F&& fn) {
 
 static std::atomic<U32> g_last_wide_sort_blocks{0};
 U32 last_wide_sort_blocks() { return g_last_wide_sort_blocks.load(std::memory_order_relaxed); }
+static std::atomic<U32> g_last_wide_parse_blocks{0};
+U32 last_wide_parse_blocks() { return g_last_wide_parse_blocks.load(std::memory_order_relaxed); }
+
+int device_parse_wide_mode() {
+  const char* knob = getenv("ZPAQ_AMD_DEVICE_PARSE_WIDE");
+  return !knob || !knob[0] ? 2 : (knob[0] != '0' ? 1 : 0);
+}
 
 // From what batch on the hash-table LZ77 parse goes to the device (DESIGN 4.5 has the measurements behind it)
 static const size_t kHashParseMinBlocks = 4;
@@ -269,18 +276,22 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     // (device/sa_wide_kernel.h), each on its own -- one such block fills the device, the four-block threshold below
     // belongs to the batched sorter.  ZPAQ_AMD_DEVICE_SORT_WIDE=0|1 forces that route off or on, unset follows sa_wide_pays;
     // ZPAQ_AMD_SORT_WIDE_FROM=<bytes> moves the split (tests: small blocks through the wide route).  A BWT block comes back as its
-    // stream, an LZ77 block as its array and the host parses with it; with ZPAQ_AMD_DEVICE_PARSE=0 the array comes back either
-    // way.  A block the route does not take, or that the device declines or fails on, is sorted by the host as before.  The other
-    // sorting blocks are a batch of their own.
+    // stream.  An LZ77 block is parsed there as well, in pieces (device/lz77_wide_kernel.h), and comes back as its
+    // list of matches or its finished stream like a batch's blocks -- ZPAQ_AMD_DEVICE_PARSE_WIDE=0|1 forces that off or on, unset
+    // follows lz_wide_parse_pays, never below 2^24 bytes; otherwise, or when the parse does not fit the budget or fails, it comes
+    // back as its array and the host parses with it.  With ZPAQ_AMD_DEVICE_PARSE=0 the array comes back either way.  A block the
+    // route does not take, or that the device declines or fails on, is sorted by the host as before.  The other sorting blocks
+    // are a batch of their own.
     U64 wide_from = 1u << 24;
     if (const char* v = getenv("ZPAQ_AMD_SORT_WIDE_FROM")) { const long long x = atoll(v); if (x > 0) wide_from = (U64)x; }
     const char* wk = getenv("ZPAQ_AMD_DEVICE_SORT_WIDE");
     const int wide_mode = !wk || !wk[0] ? 2 : (wk[0] == '0' ? 0 : 1);
     const char* pk = getenv("ZPAQ_AMD_DEVICE_PARSE");
     const bool dev_parse = !pk || pk[0] != '0';
+    const int parse_wide_mode = device_parse_wide_mode();
     std::vector<size_t> sorting;
     U64 sort_bytes = 0;
-    U32 wide_blocks = 0;
+    U32 wide_blocks = 0, wide_parsed = 0;
     for (size_t b = 0; b < nb; ++b) {
       if (!front[b].sorts) continue;
       const bool take = in[b].n >= wide_from && (wide_mode == 1 || (wide_mode == 2 && in[b].n >= (1u << 24) && sa_wide_pays(in[b].n)));
@@ -290,12 +301,16 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
       SortOut so;
       std::string note;
       bool got = false;
-      try { got = engine_sort_wide(sort_job(in[b].data, in[b].n, front[b].args), so, note, !dev_parse); } catch (const Failure&) { got = false; }   // (any device trouble: the host sorts)
-      if (got && !so.bwt.empty()) { dev_pre[b] = std::move(so); have_pre[b] = 1; }
+      const bool parse_there = dev_parse && (front[b].args[1] & 3) != 3 &&
+                               (parse_wide_mode == 1 || (parse_wide_mode == 2 && in[b].n >= (1u << 24) && lz_wide_parse_pays(in[b].n)));
+      try { got = engine_sort_wide(sort_job(in[b].data, in[b].n, front[b].args), so, note, !dev_parse, parse_there ? dev_codes : -1); }
+      catch (const Failure&) { got = false; }        // (any device trouble: the host sorts)
+      if (got && (!so.bwt.empty() || so.parsed)) { wide_parsed += so.parsed; coded_blocks += so.coded; dev_pre[b] = std::move(so); have_pre[b] = 1; }
       else if (got) dev_sa[b].swap(so.sa);
       wide_blocks += got;                            // (front[b].sorts stays true: E8E9 is done either way)
     }
     g_last_wide_sort_blocks.store(wide_blocks, std::memory_order_relaxed);
+    g_last_wide_parse_blocks.store(wide_parsed, std::memory_order_relaxed);
     // the device sorter's range is known up front (blocks below 16 MiB, 2 GiB per batch, 65535 blocks): a batch outside it
     // is left to the host sorter before anything is touched
     bool in_range = sorting.size() <= 65535 && sort_bytes < (1ull << 31);

@@ -33,6 +33,9 @@ ApiTiming last_api_timing();
 // ZPAQ_AMD_DEVICE_CODES: LZBuffer's codes of a batch the device parsed are written there as well -- 0 never, 1 always, unset
 // (2) when it pays for the batch (device/engine.hpp lz_codes_pay)
 int device_codes_mode();
+// ZPAQ_AMD_DEVICE_PARSE_WIDE: the LZ77 parse of a block the wide sorter sorted runs on the device as well (device/lz77_wide_kernel.h)
+// -- 0 never, 1 always, unset (2) where device/engine.hpp lz_wide_parse_pays says so, never below 2^24 bytes
+int device_parse_wide_mode();
 
 // Batched libzpaq::compressBlock (libzpaq.cpp:7543-7731): one archive (tag ..
 // 255) per input, all modelled payloads coded on the device in one batch.
@@ -61,6 +64,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
 
 // segments of this process's last decode_archive call that device/lz77_decode_kernel.h decoded
 U32 last_wide_sort_blocks();          // sorting blocks of this process's last compress_blocks call that the wide sorter sorted
+U32 last_wide_parse_blocks();         // ... and of those, the LZ77 blocks that were parsed on the device as well
 U32 last_device_unlz_segments();
 // ... that device/bwt_decode_kernel.h decoded
 U32 last_device_unbwt_segments();
