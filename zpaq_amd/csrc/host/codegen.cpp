@@ -367,8 +367,16 @@ static void plan_persistent(const zpq_plan& plan, PipeLayout& L, int lds_rows_wi
   // (measured against 2 and 4, profiles/r06 call 12: text 389.7 -> 395.4 MB/s, 4 MiB blocks of zeros -- MATCH's worst case -- 399 -> 431)
   static const float match_lines = [] { const char* v = getenv("ZPAQ_AMD_PACK_MATCH_LINES"); return v ? (float)atof(v) : 3.0f; }();
   const float ctx_l = G * 4 / 128.f, bh_l = G * 8 / 128.f, p_l = G * 16 / 128.f;
-  auto add = [&](int kind, int role, int sub, int unit, int lds, float cost, float lines = 0.f, float stream_lines = 0.f) {
-    PipeLayout::Slot s; s.kind = kind; s.role = role; s.sub = sub; s.unit = unit; s.lds = (lds + 255) & ~255; s.cost = cost;
+  // `issue` of a unit wavefront: the instructions of its per-byte loop (profiles/unit_isa.py on the -m5 headline chain and, for the
+  // kinds that chain does not have, on the legacy models and the all-types chain of tests/golden: static counts of the loop nest,
+  // throughput shape; profiles/r07_results.md section 1).  What the wavefronts of a SIMD share is its instruction issue: the
+  // placement inside a workgroup (`finish` below) balances these, `cost` stays what the packing into workgroups falls back on.
+  //   HCOMP 450 (310-468 by program)   ROW 347   ICM map 346   ISSE map 475   packed MIX rows 800
+  //   MIX 330 (DESIGN.md section 10's count for the halves; the static nest, which holds both ways round a clashing row, is 357-367)
+  //   CONS / AVG 115   CM 413 in the LDS, 583 in the arena   MATCH 710   MIX2 295 in the arena, 368 in the LDS   SSE 600 (estimated)
+  //   CODER 1328   per bit position: SSE 1066, CM / MIX2 as their lane-per-block forms (latency shape only: not placed by this)
+  auto add = [&](int kind, int role, int sub, int unit, int lds, float cost, float issue, float lines = 0.f, float stream_lines = 0.f) {
+    PipeLayout::Slot s; s.kind = kind; s.role = role; s.sub = sub; s.unit = unit; s.lds = (lds + 255) & ~255; s.cost = cost; s.issue = issue;
     s.lines = lines + stream_w * stream_lines;
     slots.push_back(s); ++unit_waves[unit];
   };
@@ -424,12 +432,13 @@ static void plan_persistent(const zpq_plan& plan, PipeLayout& L, int lds_rows_wi
   L.hcomp_m_lds = ph.mmask + 1u <= 256u;
   const int hbytes = (L.hcomp_h_lds ? (int)(4u * (ph.hmask + 1u)) * L.hcomp_lanes : 16) + (L.hcomp_m_lds ? (int)(ph.mmask + 1u) * L.hcomp_lanes : 0);
   // relative time per chunk of a unit wavefront inside a full launch (-m5, 1024 blocks, profiles/r05/call5: ms per 2049 chunks / 1000)
-  for (int sub = 0; sub < G / hl; ++sub) add(0, 0, sub, 0, hbytes, 0.94f, 0.f, (float)L.nctx * ctx_l * hl / G);
+  for (int sub = 0; sub < G / hl; ++sub) add(0, 0, sub, 0, hbytes, 0.94f, 450.f, 0.f, (float)L.nctx * ctx_l * hl / G);
   for (size_t r = 0; r < L.rows.size(); ++r)      // two finds per byte and block: two lines
-    add(1, (int)r, 0, row_unit[L.rows[r]], 0, 1.8f, 2.f * G * line_weight((uint64_t)comp[L.rows[r]].mask1 + 1u), ctx_l + bh_l);
+    add(1, (int)r, 0, row_unit[L.rows[r]], 0, 1.8f, 347.f, 2.f * G * line_weight((uint64_t)comp[L.rows[r]].mask1 + 1u), ctx_l + bh_l);
   for (size_t r = 0; r < L.light.size(); ++r) {
     const int k = L.light[r].first, i = L.light[r].second;
     static const float lc[12] = {0, 0, 0.1f, 2.5f, 3.1f, 0.3f, 1.5f, 2.5f, 1.43f, 0.45f, 0.45f, 0.78f};
+    static const float li[12] = {0, 0, 115.f, 583.f, 710.f, 115.f, 295.f, 600.f, 1328.f, 583.f, 295.f, 1066.f};      // issue, table in the arena
     // (the workgroups of a light unit with a lane per bit position share their code: role = the first of them, sub = which eighth of the group)
     int code_role = (int)r;
     for (size_t r2 = 0; r2 < r; ++r2) if (L.light[r2] == L.light[r]) { code_role = (int)r2; break; }
@@ -453,12 +462,13 @@ static void plan_persistent(const zpq_plan& plan, PipeLayout& L, int lds_rows_wi
     float sl = (k == K_CODER ? p_l : p_l + ctx_l) + (k == K_MIX2 || k == K_MIX2_BITS || k == K_AVG ? 2.f * p_l : (k == K_SSE || k == K_SSE_BITS ? p_l : 0.f));
     if (bits) sl *= 8.f * 8.f / (float)(G * 8);
     if (k == K_CODER && L.ps_coder_fast) lds = 4096 * 4;                 // (its table of probabilities: pipe_coder_fast)
-    add(2, code_role, L.light_sub[r], k == K_CODER ? coder_unit : p_unit[i], lds, lds && k != K_CODER ? 0.9f : lc[k < 12 ? k : 0], lines, sl);
+    add(2, code_role, L.light_sub[r], k == K_CODER ? coder_unit : p_unit[i], lds, lds && k != K_CODER ? 0.9f : lc[k < 12 ? k : 0],
+        lds && k == K_CM ? 413.f : (lds && k == K_MIX2 ? 368.f : li[k < 12 ? k : 0]), lines, sl);
   }
   // (a small chain: the whole stretch table behind the ICM's side table, device PipeStretchFull)
-  for (size_t r = 0; r < L.icm.size(); ++r) add(3, (int)r, 0, p_unit[L.icm[r]], 256 * G * 4 + (small && L.ps_icm_full ? 65536 : 0), 1.1f, 0.f, bh_l + p_l);
+  for (size_t r = 0; r < L.icm.size(); ++r) add(3, (int)r, 0, p_unit[L.icm[r]], 256 * G * 4 + (small && L.ps_icm_full ? 65536 : 0), 1.1f, 346.f, 0.f, bh_l + p_l);
   // (packed pairs: pipe_isse_packed_unit; a small chain: two words per pair and the whole squash table, pipe_isse_unit)
-  for (size_t r = 0; r < L.isse.size(); ++r) add(4, (int)r, 0, p_unit[L.isse[r]], small ? 512 * G * 4 + 8192 : 256 * G * 4 + 64 * G * 4, 1.5f, 0.f, bh_l + 2.f * p_l);
+  for (size_t r = 0; r < L.isse.size(); ++r) add(4, (int)r, 0, p_unit[L.isse[r]], small ? 512 * G * 4 + 8192 : 256 * G * 4 + 64 * G * 4, 1.5f, 475.f, 0.f, bh_l + 2.f * p_l);
   // (a wavefront of the persistent launch is 64 lanes wide whatever the group size: a MIX unit's lane groups fill it --
   //  64 / QL blocks per wavefront, not the G / QL of the step kernels' G-thread workgroups)
   // throughput shape: a MIX whose 8 rows of a byte are distinct splits the byte over two lane groups (device: pipe_mix_unit NH = 2)
@@ -493,7 +503,7 @@ static void plan_persistent(const zpq_plan& plan, PipeLayout& L, int lds_rows_wi
     if (L.mix_lds_rows[r]) lines *= 1.f / 8.f;
     for (int sub = 0; sub < nw; ++sub)
       // (every input stream: one line per wavefront and byte, whatever part of it the wavefront's blocks are)
-      add(5, (int)r, sub, p_unit[L.mix[r]], lds, L.mix_bits ? 0.55f : (L.ps_mix_nh == 2 ? 1.7f : (lds ? 1.6f : 2.6f)), lines, (float)c.a3 + ctx_l);
+      add(5, (int)r, sub, p_unit[L.mix[r]], lds, L.mix_bits ? 0.55f : (L.ps_mix_nh == 2 ? 1.7f : (lds ? 1.6f : 2.6f)), L.mix_packed[r] ? 800.f : 330.f, lines, (float)c.a3 + ctx_l);
   }
   // who reads whose streams
   std::vector<std::vector<int>> producers(nunit);
@@ -570,7 +580,40 @@ static void plan_persistent(const zpq_plan& plan, PipeLayout& L, int lds_rows_wi
       std::vector<int> v = bin_items[b];
       std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return slots[x].cost > slots[y].cost; });
       std::vector<int> at(W, -1);
-      if (W == 8) {
+      if (W == 8 && L.mode == 0) {
+        // Throughput shape: by ISSUE LOAD.  Two wavefronts of a SIMD (w and w + 4) share its instruction issue, and of the two
+        // the one with the higher wave index loses the arbitration (profiles/r06/out/c7_prof_all1.txt: a MIX wavefront beside
+        // another MIX works 2 370-2 485 ms at w = 7, 2 199-2 267 ms at w = 3, 2 222-2 229 ms beside a light or ICM wavefront).
+        // The MIX wavefronts pace the launch, so they go first, one per SIMD while a SIMD without one remains; then every
+        // other wavefront, heaviest first, to the SIMD with the smallest summed issue load that still has a free slot (an idle
+        // slot counts as 0).  Within a SIMD a MIX wavefront, then the heavier one, takes the lower wave index.
+        // Measured (profiles/r07_results.md, three alternating pairs of runs on one box): 385.5-387.3 -> 394.9-400.6 MB/s, the
+        // shortest launch 2 740 -> 2 638 ms; no SIMD holds two MIX wavefronts any more, and the slowest are now the two of the
+        // workgroup that also holds three ROW units (2 528 ms of work, 40 ms of waiting: that compute unit's memory lines).
+        std::vector<int> simd[4];
+        float load[4] = {0.f, 0.f, 0.f, 0.f};
+        std::vector<int> order = bin_items[b];
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+          if (slots[x].issue != slots[y].issue) return slots[x].issue > slots[y].issue;
+          return slots[x].cost > slots[y].cost;
+        });
+        std::vector<int> rest;
+        int next_simd = 0;
+        for (int idx : order) {
+          if (slots[idx].kind == 5 && next_simd < 4) { simd[next_simd].push_back(idx); load[next_simd] += slots[idx].issue; ++next_simd; }
+          else rest.push_back(idx);
+        }
+        for (int idx : rest) {
+          int best = -1;
+          for (int s = 0; s < 4; ++s)
+            if (simd[s].size() < 2 && (best < 0 || load[s] < load[best])) best = s;
+          simd[best].push_back(idx); load[best] += slots[idx].issue;
+        }
+        for (int s = 0; s < 4; ++s) {
+          // (the first of a SIMD is its MIX wavefront when it has one, otherwise the heavier of the two: the order they came in)
+          for (size_t k = 0; k < simd[s].size(); ++k) at[s + 4 * (int)k] = simd[s][k];
+        }
+      } else if (W == 8) {
         // two wavefronts per SIMD (w and w + 4): the units sorted by cost, the k-th heaviest shares its SIMD with the k-th lightest
         // (an idle slot counts as the lightest)
         std::vector<int> padded = v;
