@@ -14,8 +14,8 @@
 //   unbwt_link_kernel     one wavefront per tile, 64 positions at a time in order: eight ballots over the byte's bits give the
 //                         lanes with an equal byte, the rank among the lower ones places the lane, the group's highest lane adds
 //                         the group's size to the symbol's counter in LDS.  Equal bytes keep their order: that is what makes the
-//                         list the program's.  Node p's word is b << 8 | S[b]: where the walk goes and what it emits there, so a
-//                         step is one load.
+//                         list the program's.  Node p's word holds b and S[b]: where the walk goes and what it emits there, so
+//                         a step is one load.
 //   unbwt_rank_kernel     a lane per splitter -- every kBwtStride-th node, and the head idx -- walks to the next splitter (node 0,
 //                         the end, is one) and records {that splitter, steps}.
 //   unbwt_offsets_kernel  one lane per stream follows the splitters from the head: n / kBwtStride dependent steps over a table
@@ -29,6 +29,9 @@
 // by the caller: layout.h bwt_stream_admitted) the links are injective on 1 .. n and nothing points to idx, so the path from idx
 // ends at node 0 and every other walk stays on a cycle that holds its own start: every walk is bounded by n steps, whatever the
 // bytes.  Bytes that are no BWT may leave cycles beside the path; the path is then shorter than n and the stream is declined.
+//
+// Link, rank and emit are templates over the node's word (BwtNode32 here, BwtNode64 for device/bwt_decode_wide_kernel.h): how b
+// and S[b] are packed into it is all that the two forms' lists differ in.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -38,6 +41,25 @@
 #include "layout.h"
 
 namespace zpq {
+
+static const uint32_t kBwtOff = 0xFFFFFFFFu;        // a splitter's next: dead; its offset: not on the path
+
+// A node's word, by its type: the position the walk goes to and the byte it emits there.  Link, rank and emit take the form
+// from the type of the list they are given.  4 bytes, b << 8 | S[b]: positions below 2^24.
+template <class Word> struct BwtNode;
+template <> struct BwtNode<uint32_t> {
+  static __device__ __forceinline__ uint32_t pack(uint32_t node, uint32_t v) { return node << 8 | v; }
+  static __device__ __forceinline__ uint32_t next(uint32_t w) { return w >> 8; }
+  static __device__ __forceinline__ uint32_t byte(uint32_t w) { return w & 255u; }
+};
+// 8 bytes, (uint64_t)S[b] << 32 | b: a full 32-bit position, one 8-byte store of the lane that owns position b
+template <> struct BwtNode<uint64_t> {
+  static __device__ __forceinline__ uint64_t pack(uint32_t node, uint32_t v) { return (uint64_t)v << 32 | node; }
+  static __device__ __forceinline__ uint32_t next(uint64_t w) { return (uint32_t)w; }
+  static __device__ __forceinline__ uint32_t byte(uint64_t w) { return (uint32_t)(w >> 32) & 255u; }
+};
+typedef BwtNode<uint32_t> BwtNode32;
+typedef BwtNode<uint64_t> BwtNode64;
 
 // the stream a tile / a splitter belongs to: the last one that starts at or below g (every stream has some of each)
 __device__ __forceinline__ uint32_t unbwt_stream_of_tile(const BwtStream* streams, uint32_t nstreams, uint32_t g) {
@@ -100,14 +122,15 @@ __device__ __forceinline__ void unbwt_scan_body(const BwtStream* streams, uint32
 }
 
 // (c) one wavefront per tile (64 threads per workgroup); link: node p of stream b at link_all[link_off + p]
+template <class Word>
 __device__ __forceinline__ void unbwt_link_body(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
-                                                uint32_t* link_all) {
+                                                Word* link_all) {
   __shared__ uint32_t base[256];
   const uint32_t g = blockIdx.x, lane = threadIdx.x & 63u;
   const BwtStream S = streams[unbwt_stream_of_tile(streams, nstreams, g)];
   const uint32_t first = (g - S.tile_off) * (uint32_t)kBwtTile;
   const uint8_t* s = in_all + S.in_off;
-  uint32_t* link = link_all + S.link_off;
+  Word* link = link_all + S.link_off;
   const unsigned long long below = (1ull << lane) - 1ull;
   for (uint32_t k = 0; k < 4u; ++k) base[lane + 64u * k] = hist[(uint64_t)g * 256u + lane + 64u * k];
   __syncthreads();
@@ -124,7 +147,7 @@ __device__ __forceinline__ void unbwt_link_body(const uint8_t* in_all, const Bwt
       same &= bit ? m : ~m;
     }
     const uint32_t rank = (uint32_t)__builtin_popcountll(same & below), size = (uint32_t)__builtin_popcountll(same);
-    if (live) link[base[v] + rank] = node << 8 | v;
+    if (live) link[base[v] + rank] = BwtNode<Word>::pack(node, v);
     __syncthreads();                                            // (every lane has read its counter)
     if (live && rank + 1u == size) base[v] += size;
     __syncthreads();
@@ -132,18 +155,20 @@ __device__ __forceinline__ void unbwt_link_body(const uint8_t* in_all, const Bwt
 }
 
 // (d) a lane per splitter of the batch (nsplit of them); sp: {next splitter, steps, output offset, -}
-__device__ __forceinline__ void unbwt_rank_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link_all, uint4* sp) {
+template <class Word>
+__device__ __forceinline__ void unbwt_rank_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const Word* link_all,
+                                                uint4* sp) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nsplit) return;
   const BwtStream S = streams[unbwt_stream_of_splitter(streams, nstreams, g)];
   const uint32_t j = g - S.sp_off, head = S.n / (uint32_t)kBwtStride + 1u;
   uint4 r;
-  r.x = 0u; r.y = 0u; r.z = 0xFFFFFFFFu; r.w = 0u;              // z: not on the path, until the offsets say otherwise
+  r.x = 0u; r.y = 0u; r.z = kBwtOff; r.w = 0u;                  // z: not on the path, until the offsets say otherwise
   if (j) {
-    const uint32_t* link = link_all + S.link_off;
+    const Word* link = link_all + S.link_off;
     uint32_t d = j == head ? S.idx : j * (uint32_t)kBwtStride, steps = 0;
-    do { d = link[d] >> 8; ++steps; } while ((d & ((uint32_t)kBwtStride - 1u)) && steps < S.n);
-    r.x = (d & ((uint32_t)kBwtStride - 1u)) ? 0xFFFFFFFFu : d / (uint32_t)kBwtStride;
+    do { d = BwtNode<Word>::next(link[d]); ++steps; } while ((d & ((uint32_t)kBwtStride - 1u)) && steps < S.n);
+    r.x = (d & ((uint32_t)kBwtStride - 1u)) ? kBwtOff : d / (uint32_t)kBwtStride;
     r.y = steps;
   }
   sp[g] = r;
@@ -175,8 +200,9 @@ __device__ __forceinline__ void unbwt_flush(uint8_t* out, uint64_t from, uint64_
 }
 
 // (f) a lane per splitter of the batch; stream b's output at out_all + out_off
-__device__ __forceinline__ void unbwt_emit_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint32_t* link_all, const uint4* sp,
-                                                const uint32_t* status, uint8_t* out_all) {
+template <class Word>
+__device__ __forceinline__ void unbwt_emit_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const Word* link_all,
+                                                const uint4* sp, const uint32_t* status, uint8_t* out_all) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= nsplit) return;
   const uint32_t b = unbwt_stream_of_splitter(streams, nstreams, g);
@@ -184,15 +210,15 @@ __device__ __forceinline__ void unbwt_emit_body(const BwtStream* streams, uint32
   const BwtStream S = streams[b];
   const uint32_t j = g - S.sp_off, head = S.n / (uint32_t)kBwtStride + 1u;
   const uint4 e = sp[g];
-  if (!j || e.z == 0xFFFFFFFFu) return;
-  const uint32_t* link = link_all + S.link_off;
+  if (!j || e.z == kBwtOff) return;
+  const Word* link = link_all + S.link_off;
   uint8_t* out = out_all;
   uint64_t pos = S.out_off + e.z, from = pos;
   uint32_t d = j == head ? S.idx : j * (uint32_t)kBwtStride, acc = 0;
   for (uint32_t k = 0; k < e.y; ++k) {
-    const uint32_t w = link[d];
-    d = w >> 8;
-    acc |= (w & 255u) << (8u * (uint32_t)((uintptr_t)(out + pos) & 3u));
+    const Word w = link[d];
+    d = BwtNode<Word>::next(w);
+    acc |= BwtNode<Word>::byte(w) << (8u * (uint32_t)((uintptr_t)(out + pos) & 3u));
     ++pos;
     if (((uintptr_t)(out + pos) & 3u) == 0u) { unbwt_flush(out, from, pos, acc); acc = 0u; from = pos; }
   }

@@ -4,7 +4,9 @@
 // position, so the 24-bit limit of device/bwt_decode_kernel.h is gone and n goes up to 2^31 - 257.
 //
 // The stream, the order (S[b], b), the rule and the stages are those of the small decoder, whose count kernel serves both forms
-// as it is (a tile's 256 words do not depend on the width of a node).  What differs:
+// as it is (a tile's 256 words do not depend on the width of a node).  Link, the splitters' rank and emit are the small decoder's
+// bodies too, over 8-byte words (BwtNode64: (uint64_t)S[b] << 32 | b, one 8-byte store of the lane that owns position b, so a step
+// of either walk stays one load).  What is here:
 //
 //   unbwt_wide_scan_kernel     one workgroup of 1 024 per stream, thread = (part, symbol): unbwt_scan_kernel loops over all tiles of
 //                              a stream twice with one wavefront per 64 symbols -- 16 384 tiles for a default block, the longest
@@ -12,9 +14,6 @@
 //                              sums its range, the parts' sums give the totals and every part's base, the same scan over the
 //                              symbols follows, and each part turns its range's counts into first nodes.  Four tiles per step, the
 //                              loads in front of the stores.
-//   unbwt_wide_link_kernel     as unbwt_link_kernel, but node p's word is (uint64_t)S[b] << 32 | b, one 8-byte store of the lane that
-//                              owns position b: a step of either walk stays one load.
-//   unbwt_wide_rank_kernel     a lane per splitter walks the 8-byte words to the next splitter: {that splitter, steps}.
 //   unbwt_wide_rank2_kernel    the splitter list is ranked as the node list is: every kBwtStride2-th splitter index, and the head,
 //                              is a second-level splitter.  A lane per second-level splitter walks the splitter list to the next
 //                              one (splitter 0, the end, is one) and records {that one, nodes on the way, -, splitters on the way}.
@@ -22,13 +21,12 @@
 //                              the small form makes n / 256.  Each second-level sublist on the path receives its output offset;
 //                              the total is the length of the path, and anything but n declines the stream (status 1).
 //   unbwt_wide_offsets1_kernel a lane per second-level splitter on the path walks its splitters again and hands each its offset.
-//   unbwt_wide_emit_kernel     as unbwt_emit_kernel over the 8-byte words.
 //
 // Stage boundaries are kernel boundaries; no workgroup waits for another.  Under the rule the links are injective on 1 .. n and
 // nothing points to idx, so the same holds one level up: the map splitter -> next splitter is injective where it is defined,
 // nothing leads to the head, the path from the head ends at entry 0 and every other walk stays on a cycle that holds its own
 // start.  Every walk is bounded by the count of its level; a walk that meets an entry marked dead (its node walk ran into its
-// bound) is dead itself; entries off the path keep 0xFFFFFFFF as their offset and emit nothing.
+// bound) is dead itself; entries off the path keep kBwtOff as their offset and emit nothing.
 //
 // 32-bit arithmetic: n <= 2^31 - 257, so a position, a position + 4 095 (the end of its tile), tile * kBwtTile and
 // splitter * kBwtStride stay below 2^32; sums of steps are bounded by n where the walk is live and are taken in 64 bits where a
@@ -43,8 +41,6 @@
 #include "layout.h"
 
 namespace zpq {
-
-static const uint32_t kBwtOff = 0xFFFFFFFFu;        // a splitter's next: dead; its offset: not on the path
 
 // the stream a second-level splitter belongs to: the last one whose table starts at or below g
 __device__ __forceinline__ uint32_t unbwt_stream_of_splitter2(const uint32_t* sp2_off, uint32_t nstreams, uint32_t g) {
@@ -102,56 +98,6 @@ __device__ __forceinline__ void unbwt_wide_scan_body(const BwtStream* streams, u
     h[(uint64_t)t * 256u] = run;
     run += c;
   }
-}
-
-// (c) one wavefront per tile (64 threads per workgroup); link: node p of stream b at link_all[link_off + p]
-__device__ __forceinline__ void unbwt_wide_link_body(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
-                                                     uint64_t* link_all) {
-  __shared__ uint32_t base[256];
-  const uint32_t g = blockIdx.x, lane = threadIdx.x & 63u;
-  const BwtStream S = streams[unbwt_stream_of_tile(streams, nstreams, g)];
-  const uint32_t first = (g - S.tile_off) * (uint32_t)kBwtTile;
-  const uint8_t* s = in_all + S.in_off;
-  uint64_t* link = link_all + S.link_off;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (uint32_t k = 0; k < 4u; ++k) base[lane + 64u * k] = hist[(uint64_t)g * 256u + lane + 64u * k];
-  __syncthreads();
-  for (uint32_t c = 0; c < (uint32_t)kBwtTile / (uint32_t)kBwtChunk; ++c) {
-    const uint32_t p0 = first + c * (uint32_t)kBwtChunk;
-    if (p0 > S.n) break;                                        // (the same in every lane)
-    const uint32_t node = p0 + lane;
-    const bool live = node <= S.n && node != S.idx;
-    const uint32_t v = node <= S.n ? s[node] : 0u;
-    unsigned long long same = __builtin_amdgcn_ballot_w64(live);
-    for (uint32_t k = 0; k < 8u; ++k) {
-      const bool bit = (v >> k) & 1u;
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(bit);
-      same &= bit ? m : ~m;
-    }
-    const uint32_t rank = (uint32_t)__builtin_popcountll(same & below), size = (uint32_t)__builtin_popcountll(same);
-    if (live) link[base[v] + rank] = (uint64_t)v << 32 | node;
-    __syncthreads();                                            // (every lane has read its counter)
-    if (live && rank + 1u == size) base[v] += size;
-    __syncthreads();
-  }
-}
-
-// (d) a lane per splitter of the batch (nsplit of them); sp: {next splitter, steps, output offset, -}
-__device__ __forceinline__ void unbwt_wide_rank_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link_all, uint4* sp) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= nsplit) return;
-  const BwtStream S = streams[unbwt_stream_of_splitter(streams, nstreams, g)];
-  const uint32_t j = g - S.sp_off, head = S.n / (uint32_t)kBwtStride + 1u;
-  uint4 r;
-  r.x = 0u; r.y = 0u; r.z = kBwtOff; r.w = 0u;                  // z: not on the path, until the offsets say otherwise
-  if (j) {
-    const uint64_t* link = link_all + S.link_off;
-    uint32_t d = j == head ? S.idx : j * (uint32_t)kBwtStride, steps = 0;
-    do { d = (uint32_t)link[d]; ++steps; } while ((d & ((uint32_t)kBwtStride - 1u)) && steps < S.n);
-    r.x = (d & ((uint32_t)kBwtStride - 1u)) ? kBwtOff : d / (uint32_t)kBwtStride;
-    r.y = steps;
-  }
-  sp[g] = r;
 }
 
 // (e1) a lane per second-level splitter of the batch (nsplit2 of them); sp2: {next second-level splitter, nodes, output offset, splitters}
@@ -226,29 +172,18 @@ __device__ __forceinline__ void unbwt_wide_offsets1_body(const BwtStream* stream
   }
 }
 
-// (f) a lane per splitter of the batch; stream b's output at out_all + out_off
+// (c), (d), (f): the small decoder's bodies, which take the form from the list's word.  The names they had as bodies of their own,
+// for sources written against those
+__device__ __forceinline__ void unbwt_wide_link_body(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
+                                                     uint64_t* link_all) {
+  unbwt_link_body(in_all, streams, nstreams, hist, link_all);
+}
+__device__ __forceinline__ void unbwt_wide_rank_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link_all, uint4* sp) {
+  unbwt_rank_body(streams, nstreams, nsplit, link_all, sp);
+}
 __device__ __forceinline__ void unbwt_wide_emit_body(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link_all,
                                                      const uint4* sp, const uint32_t* status, uint8_t* out_all) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= nsplit) return;
-  const uint32_t b = unbwt_stream_of_splitter(streams, nstreams, g);
-  if (status[b] != 0u) return;
-  const BwtStream S = streams[b];
-  const uint32_t j = g - S.sp_off, head = S.n / (uint32_t)kBwtStride + 1u;
-  const uint4 e = sp[g];
-  if (!j || e.z == kBwtOff) return;
-  const uint64_t* link = link_all + S.link_off;
-  uint8_t* out = out_all;
-  uint64_t pos = S.out_off + e.z, from = pos;
-  uint32_t d = j == head ? S.idx : j * (uint32_t)kBwtStride, acc = 0;
-  for (uint32_t k = 0; k < e.y; ++k) {
-    const uint64_t w = link[d];
-    d = (uint32_t)w;
-    acc |= ((uint32_t)(w >> 32) & 255u) << (8u * (uint32_t)((uintptr_t)(out + pos) & 3u));
-    ++pos;
-    if (((uintptr_t)(out + pos) & 3u) == 0u) { unbwt_flush(out, from, pos, acc); acc = 0u; from = pos; }
-  }
-  if (from < pos) unbwt_flush(out, from, pos, acc);
+  unbwt_emit_body(streams, nstreams, nsplit, link_all, sp, status, out_all);
 }
 
 }  // namespace zpq

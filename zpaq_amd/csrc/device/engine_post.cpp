@@ -143,6 +143,28 @@ static bool une8_run(Engine& e, uint64_t ws_off, const std::vector<E8Block>& blk
   return true;
 }
 
+// The decoded blocks of a batch as the filter takes them: add() those that are live in the order they lie in io_out (i: the
+// caller's index of the block), then run() over them.  tiles and ws_bytes(): what the list as it stands asks of the budget.
+struct E8List {
+  std::vector<E8Block> blk;
+  std::vector<size_t> who;
+  uint64_t tiles = 0;
+  void add(size_t i, uint64_t off, uint32_t n) {
+    blk.push_back(E8Block{off, n, (uint32_t)tiles});
+    who.push_back(i);
+    tiles += e8_tiles(n);
+  }
+  uint64_t ws_bytes() const { return une8_ws(blk.size(), tiles).bytes; }
+  // une8_run over the list; lost[i] = 1 (of `count` caller's blocks): a lane gave block i up.  false + note: as une8_run
+  bool run(Engine& e, uint64_t ws_off, uint64_t held, size_t count, std::vector<char>& lost, std::string& note) const {
+    std::vector<uint32_t> st;
+    lost.assign(count, 0);
+    if (!une8_run(e, ws_off, blk, tiles, held, st, note)) return false;
+    for (size_t k = 0; k < blk.size(); ++k) if (st[k] != 0) lost[who[k]] = 1;
+    return true;
+  }
+};
+
 // device/lz77_decode_kernel.h for a batch of host streams: one upload, the parse, 12 bytes per stream back, the outputs placed
 // back to back (sizes first, then emission: no bound is guessed), the copy, the outputs down.  e8: the method's program filters
 // M before it writes it out -- the outputs are placed for device/e8e9_kernel.h, which runs over them before they go down.
@@ -190,28 +212,22 @@ static int lz77_decode_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::v
   HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, n * sizeof(UnlzResult), hipMemcpyDeviceToHost, e.stream));
   HIP_CHECK(hipStreamSynchronize(e.stream));
   std::vector<uint64_t> off(n);
-  uint64_t room = 0, tiles = 0;
+  uint64_t room = 0;
   bool fits = true, any = false;
-  std::vector<E8Block> fb;                          // e8: the decoded blocks as the filter sees them, fb[k] is jobs[fwho[k]]
-  std::vector<size_t> fwho;
+  E8List fl;                                        // e8: the decoded blocks as the filter sees them
   for (size_t i = 0; i < n; ++i) {
     off[i] = room;
     if (res[i].status != kUnlzOk) continue;
     jobs[i].out_len = res[i].out_len;
-    if (e8) {
-      fb.push_back(E8Block{room, res[i].out_len, (uint32_t)tiles});
-      fwho.push_back(i);
-      tiles += e8_tiles(res[i].out_len);
-    }
+    if (e8) fl.add(i, room, res[i].out_len);
     room += e8 ? e8_room(res[i].out_len) : res[i].out_len;
     any = true;
     if (!jobs[i].vec && res[i].out_len > jobs[i].cap) fits = false;
   }
   if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
-  const uint64_t f_off = e8 ? align_up(room, 256) : room, f_ws = e8 ? une8_ws(fb.size(), tiles).bytes : 0;
+  const uint64_t f_off = e8 ? align_up(room, 256) : room, f_ws = e8 ? fl.ws_bytes() : 0;
   if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; return declined(jobs); }
   if (!fits) return 0;
-  std::vector<uint32_t> fst;
   if (any) {
     e.io_out.ensure(f_off + f_ws + 64);
     HIP_CHECK(hipMemcpyAsync(ab + o_off, off.data(), 8 * n, hipMemcpyHostToDevice, e.stream));
@@ -219,8 +235,9 @@ static int lz77_decode_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::v
                           (const uint64_t*)(ab + o_off), (uint8_t*)e.io_out.p, e.stream);
     if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return declined(jobs);
     if (e8) {
-      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) return declined(jobs);
-      for (size_t k = 0; k < fb.size(); ++k) if (fst[k] != 0) { res[fwho[k]].status = kUnlzLong; jobs[fwho[k]].out_len = 0; }
+      std::vector<char> lost;
+      if (!fl.run(e, f_off, ws + f_off + f_ws, n, lost, note)) return declined(jobs);
+      for (size_t i = 0; i < n; ++i) if (lost[i]) { res[i].status = kUnlzLong; jobs[i].out_len = 0; }
     }
     for (size_t i = 0; i < n; ++i) {
       if (res[i].status != kUnlzOk) continue;
@@ -235,222 +252,168 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
   return lz77_decode_batch(level, rb, min_match, mbits, jobs, note, false);
 }
 
-// device/bwt_decode_kernel.h for a batch of host streams.  The host admits the streams (the rule, the range), so every size is
-// known and the room is checked before anything runs; then one upload, the six kernels, a word per stream back, and the outputs
-// of the streams whose path was whole down.  e8: as for lz77_decode_batch.
+// The BWT decoders, device/bwt_decode_kernel.h (4-byte nodes, blocks below 16 MiB) and device/bwt_decode_wide_kernel.h (8-byte
+// nodes, the program at args[0] 5 .. 11), for a batch of host streams.  The host admits the streams (the rule, the range), so
+// every size is known and the room is checked before anything runs; then one upload, the kernels, a word per stream back, and the
+// outputs of the streams whose path was whole down.  e8: as for lz77_decode_batch.
+
+// The host's step: admitted stream k is jobs[who[k]], n[k] bytes (reported in out_len) with the marker at idx[k]; empty[i]: job i
+// is the empty block's stream; fits: every admitted stream has room in its job's buffer
+struct BwtAdmitted {
+  std::vector<size_t> who;
+  std::vector<uint32_t> n, idx;
+  std::vector<char> empty;
+  bool fits = true;
+};
+static BwtAdmitted bwt_admit(bool wide, U32 mbits, std::vector<StreamJob>& jobs) {
+  BwtAdmitted a;
+  a.empty.assign(jobs.size(), 0);
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    StreamJob& j = jobs[i];
+    if (bwt_stream_empty(j.in, j.in_len)) { a.empty[i] = 1; continue; }
+    uint32_t sn = 0, sidx = 0;
+    if (!(wide ? bwt_wide_stream_admitted(j.in, j.in_len, mbits, sn, sidx) : bwt_stream_admitted(j.in, j.in_len, mbits, sn, sidx))) continue;
+    j.out_len = sn;
+    if (!j.vec && sn > j.cap) a.fits = false;
+    a.who.push_back(i);
+    a.n.push_back(sn);
+    a.idx.push_back(sidx);
+  }
+  return a;
+}
+// the call's end when the device did its part: the empty blocks' streams are decoded too
+static int bwt_done(std::vector<StreamJob>& jobs, const BwtAdmitted& a) {
+  for (size_t i = 0; i < jobs.size(); ++i) if (a.empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
+  return 1;
+}
+
+// Admitted streams from .. end as one batch on the device (layout.h BwtNeed): st[k] and s2[k] are stream from + k's
+struct BwtPlaced {
+  BwtNeed w;
+  std::vector<BwtStream> st;
+  std::vector<uint32_t> s2;                         // where the streams' second-level tables start (the wide form's)
+};
+static BwtPlaced bwt_place(const BwtAdmitted& a, size_t from, size_t end, bool e8) {
+  BwtPlaced p;
+  p.st.resize(end - from);
+  p.s2.resize(end - from);
+  for (size_t k = 0; k < end - from; ++k) p.st[k] = p.w.place(a.n[from + k], a.idx[from + k], e8, &p.s2[k]);
+  return p;
+}
+
+// One placed batch of either width, stream k of which is jobs[who[k]]: carve the arena, check the budget, stage, launch, read
+// the statuses, filter, deliver.  kBwtRan: status and out_len of its jobs are final.  Otherwise nothing of it was delivered and
+// `note` says why -- kBwtOver: it does not fit the budget; kBwtBroken: a launch or the runtime failed.
+enum { kBwtBroken = -1, kBwtOver = 0, kBwtRan = 1 };
+static int bwt_run(Engine& e, bool wide, bool e8, std::vector<StreamJob>& jobs, const size_t* who, const BwtPlaced& p, std::string& note) {
+  const size_t m = p.st.size();
+  const BwtNeed& w = p.w;
+  // the arena buffer (idle between batches): the list, the tile histograms, the splitter tables, the stream tables, the statuses
+  Carve cv;
+  cv.take((wide ? 8 : 4) * w.nodes);
+  const uint64_t o_hist = cv.take(1024 * w.tiles);
+  const uint64_t o_sp = cv.take(16 * w.splits);
+  const uint64_t o_sp2 = wide ? cv.take(16 * w.splits2) : 0;
+  const uint64_t o_st = cv.take(m * sizeof(BwtStream));
+  const uint64_t o_s2 = wide ? cv.take(4 * m) : 0;
+  const uint64_t o_res = cv.take(4 * m);
+  const uint64_t ws = cv.at + 256;
+  uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
+  for (size_t k = 0; k < m && e8; ++k) f_tiles += e8_tiles(p.st[k].n);
+  const uint64_t f_off = e8 ? align_up(w.room, 256) : w.room, f_ws = e8 ? une8_ws(m, f_tiles).bytes : 0;
+  if (ws + w.in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return kBwtOver; }
+  e.io_in.ensure(w.in_bytes + 64);
+  e.io_out.ensure(f_off + f_ws + 64);
+  e.arena.ensure(ws);
+  uint8_t* const ab = (uint8_t*)e.arena.p;
+  std::vector<HostItem> items(m);
+  for (size_t k = 0; k < m; ++k) items[k] = HostItem{jobs[who[k]].in, jobs[who[k]].in_len, p.st[k].in_off};
+  const auto staged = upload_staged(e, e.io_in.p, items, w.in_bytes, 4, false);
+  HIP_CHECK(hipMemcpyAsync(ab + o_st, p.st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
+  if (wide) HIP_CHECK(hipMemcpyAsync(ab + o_s2, p.s2.data(), 4 * m, hipMemcpyHostToDevice, e.stream));
+  const uint8_t* const in_all = (const uint8_t*)e.io_in.p;
+  const BwtStream* const d_st = (const BwtStream*)(ab + o_st);
+  uint32_t* const d_hist = (uint32_t*)(ab + o_hist);
+  uint32_t* const d_res = (uint32_t*)(ab + o_res);
+  const hipError_t rc =
+      wide ? launch_bwt_decode_wide(in_all, d_st, (const uint32_t*)(ab + o_s2), (uint32_t)m, (uint32_t)w.tiles, (uint32_t)w.splits, (uint32_t)w.splits2,
+                                    d_hist, (uint64_t*)ab, ab + o_sp, ab + o_sp2, d_res, (uint8_t*)e.io_out.p, e.stream)
+           : launch_bwt_decode(in_all, d_st, (uint32_t)m, (uint32_t)w.tiles, (uint32_t)w.splits, d_hist, (uint32_t*)ab, ab + o_sp, d_res,
+                               (uint8_t*)e.io_out.p, e.stream);
+  if (launch_failed(rc, "device BWT decoder failed: ", note)) return kBwtBroken;
+  std::vector<uint32_t> res(m);
+  HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (e8) {
+    E8List fl;
+    std::vector<char> lost;
+    for (size_t k = 0; k < m; ++k) if (res[k] == 0) fl.add(k, p.st[k].out_off, p.st[k].n);
+    // (a list beyond the budget is this batch's size, no failure of the device)
+    if (!fl.run(e, f_off, ws + f_off + f_ws, m, lost, note)) return note.find("budget") == std::string::npos ? kBwtBroken : kBwtOver;
+    for (size_t k = 0; k < m; ++k) if (lost[k]) res[k] = 1u;
+  }
+  for (size_t k = 0; k < m; ++k) {
+    StreamJob& j = jobs[who[k]];
+    if (res[k] != 0) { j.out_len = 0; continue; }
+    deliver(e, j, p.st[k].out_off, p.st[k].n);
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
+  return kBwtRan;
+}
+
+// The small form: the batch as a whole or not at all -- whatever keeps it from running declines it (-1 + note).
 static int bwt_decode_batch(U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
   const size_t n = jobs.size();
   if (!n) return 1;
   for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
   if (n > 65535 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
-  std::vector<BwtStream> st;
-  std::vector<size_t> who;                          // st[k] is jobs[who[k]]
-  std::vector<char> empty(n, 0);
-  uint64_t in_bytes = 0, nodes = 0, tiles = 0, splits = 0, room = 0;
-  bool fits = true;
-  for (size_t i = 0; i < n; ++i) {
-    const StreamJob& j = jobs[i];
-    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
-    BwtStream S;
-    memset(&S, 0, sizeof(S));
-    if (!bwt_stream_admitted(j.in, j.in_len, mbits, S.n, S.idx)) continue;
-    S.in_off = in_bytes;
-    S.link_off = nodes;
-    S.out_off = room;
-    S.tile_off = (uint32_t)tiles;
-    S.sp_off = (uint32_t)splits;
-    in_bytes += align_up(j.in_len, 4);
-    nodes += (uint64_t)S.n + 1;
-    tiles += bwt_tiles(S.n);
-    splits += bwt_splitters(S.n);
-    room += e8 ? e8_room(S.n) : S.n;
-    jobs[i].out_len = S.n;
-    if (!j.vec && S.n > j.cap) fits = false;
-    st.push_back(S);
-    who.push_back(i);
-  }
-  const size_t m = st.size();
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
-  if (!fits) return 0;
-  if (m) {
+  const BwtAdmitted a = bwt_admit(false, mbits, jobs);
+  const BwtPlaced p = bwt_place(a, 0, a.who.size(), e8);
+  if (p.w.room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return declined(jobs); }
+  if (!a.fits) return 0;
+  if (!a.who.empty()) {
     EngineCall call;
-    Engine& e = call.e;
-    // the arena buffer (idle between batches): the list, the tile histograms, the splitters, the stream table, the statuses
-    Carve cv;
-    cv.take(4 * nodes);
-    const uint64_t o_hist = cv.take(1024 * tiles);
-    const uint64_t o_sp = cv.take(16 * splits);
-    const uint64_t o_st = cv.take(m * sizeof(BwtStream));
-    const uint64_t o_res = cv.take(4 * m);
-    const uint64_t ws = cv.at + 256;
-    uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
-    for (size_t k = 0; k < m && e8; ++k) f_tiles += e8_tiles(st[k].n);
-    const uint64_t f_off = e8 ? align_up(room, 256) : room, f_ws = e8 ? une8_ws(m, f_tiles).bytes : 0;
-    if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return declined(jobs); }
-    e.io_in.ensure(in_bytes + 64);
-    e.io_out.ensure(f_off + f_ws + 64);
-    e.arena.ensure(ws);
-    uint8_t* const ab = (uint8_t*)e.arena.p;
-    std::vector<HostItem> items(m);
-    for (size_t k = 0; k < m; ++k) items[k] = HostItem{jobs[who[k]].in, jobs[who[k]].in_len, st[k].in_off};
-    const auto staged = upload_staged(e, e.io_in.p, items, in_bytes, 4, false);
-    HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
-    const hipError_t rc = launch_bwt_decode((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (uint32_t)m, (uint32_t)tiles, (uint32_t)splits,
-                                            (uint32_t*)(ab + o_hist), (uint32_t*)ab, ab + o_sp, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
-    if (launch_failed(rc, "device BWT decoder failed: ", note)) return declined(jobs);
-    std::vector<uint32_t> res(m);
-    HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * m, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    if (e8) {
-      std::vector<E8Block> fb;
-      std::vector<size_t> fk;
-      std::vector<uint32_t> fst;
-      uint64_t tiles = 0;
-      for (size_t k = 0; k < m; ++k) {
-        if (res[k] != 0) continue;
-        fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
-        fk.push_back(k);
-        tiles += e8_tiles(st[k].n);
-      }
-      if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) return declined(jobs);
-      for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
-    }
-    for (size_t k = 0; k < m; ++k) {
-      StreamJob& j = jobs[who[k]];
-      if (res[k] != 0) { j.out_len = 0; continue; }
-      deliver(e, j, st[k].out_off, st[k].n);
-    }
-    HIP_CHECK(hipStreamSynchronize(e.stream));
-    for (size_t k = 0; k < m; ++k) if (res[k] == 0) jobs[who[k]].status = 0;
+    if (bwt_run(call.e, false, e8, jobs, a.who.data(), p, note) != kBwtRan) return declined(jobs);
   }
-  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
-  return 1;
+  return bwt_done(jobs, a);
 }
 int engine_bwt_decode(U32 mbits, std::vector<StreamJob>& jobs, std::string& note) { return bwt_decode_batch(mbits, jobs, note, false); }
 
-// device/bwt_decode_wide_kernel.h for a batch of host streams: the program at args[0] 5 .. 11 (mbits 25 .. 31).  The order is
-// bwt_decode_batch's -- admit, size, report an overflow with every size and nothing launched, check the budget, launch, deliver --
-// but these blocks are large: a batch whose outputs exceed 2 GiB or whose workspace exceeds the budget is cut into consecutive
-// sub-batches that each fit (layout.h bwt_wide_cut), which run one after the other through the same buffers.  Only a stream that
-// does not fit alone is declined (status 1 + note; -1 when nothing else was decoded either).  After a failed launch nothing more
-// is started: that sub-batch and every stream behind it are declined.
+// The wide form (mbits 25 .. 31).  These blocks are large: a batch whose outputs exceed 2 GiB or whose workspace exceeds the budget
+// is cut into consecutive sub-batches that each fit (layout.h bwt_wide_cut), which run one after the other through the same
+// buffers.  Only a stream that does not fit alone is declined (status 1 + note; -1 when nothing else was decoded either).  After a
+// failed launch nothing more is started: that sub-batch and every stream behind it are declined.
 static int bwt_decode_wide_batch(U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
   const size_t n = jobs.size();
   if (!n) return 1;
   for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
   if (mbits < 25 || mbits > 31) { note = "batch outside the device decoder's range"; return -1; }
-  std::vector<size_t> who;                          // admitted stream k is jobs[who[k]]
-  std::vector<uint32_t> ns, idxs;
-  std::vector<char> empty(n, 0);
-  bool fits = true;
-  for (size_t i = 0; i < n; ++i) {
-    const StreamJob& j = jobs[i];
-    if (bwt_stream_empty(j.in, j.in_len)) { empty[i] = 1; continue; }
-    uint32_t sn = 0, sidx = 0;
-    if (!bwt_wide_stream_admitted(j.in, j.in_len, mbits, sn, sidx)) continue;
-    jobs[i].out_len = sn;
-    if (!j.vec && sn > j.cap) fits = false;
-    who.push_back(i);
-    ns.push_back(sn);
-    idxs.push_back(sidx);
-  }
-  if (!fits) return 0;
-  const size_t m = who.size();
+  const BwtAdmitted a = bwt_admit(true, mbits, jobs);
+  if (!a.fits) return 0;
+  const size_t m = a.who.size();
   bool some = false, left = false;
   if (m) {
     EngineCall call;
     Engine& e = call.e;
     // (the filter's own tables are about 8 bytes per 4 KiB tile: the cut leaves them 1/256 of the budget)
     const uint64_t spare = (1u << 20) + (e8 ? e.budget / 256 : 0), held_limit = e.budget > spare ? e.budget - spare : 0;
-    bool broken = false;                              // a launch or the runtime failed: nothing more is started on the device
-    auto run = [&](size_t from, size_t end) -> bool {
-      const size_t mm = end - from;
-      std::vector<BwtStream> st(mm);
-      std::vector<uint32_t> s2(mm);
-      BwtWideNeed w;
-      for (size_t k = 0; k < mm; ++k) {
-        BwtStream& S = st[k];
-        memset(&S, 0, sizeof(S));
-        S.n = ns[from + k];
-        S.idx = idxs[from + k];
-        S.in_off = w.in_bytes;
-        S.link_off = w.nodes;
-        S.out_off = w.room;
-        S.tile_off = (uint32_t)w.tiles;
-        S.sp_off = (uint32_t)w.splits;
-        s2[k] = (uint32_t)w.splits2;
-        w.add(S.n, e8);
-      }
-      // the arena buffer (idle between batches): the list, the tile histograms, the two splitter tables, the stream tables, the statuses
-      Carve cv;
-      cv.take(8 * w.nodes);
-      const uint64_t o_hist = cv.take(1024 * w.tiles);
-      const uint64_t o_sp = cv.take(16 * w.splits);
-      const uint64_t o_sp2 = cv.take(16 * w.splits2);
-      const uint64_t o_st = cv.take(mm * sizeof(BwtStream));
-      const uint64_t o_s2 = cv.take(4 * mm);
-      const uint64_t o_res = cv.take(4 * mm);
-      const uint64_t ws = cv.at + 256;
-      uint64_t f_tiles = 0;                             // e8: the filter's tiles, were every stream decoded
-      for (size_t k = 0; k < mm && e8; ++k) f_tiles += e8_tiles(st[k].n);
-      const uint64_t f_off = e8 ? align_up(w.room, 256) : w.room, f_ws = e8 ? une8_ws(mm, f_tiles).bytes : 0;
-      if (ws + w.in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return false; }
-      e.io_in.ensure(w.in_bytes + 64);
-      e.io_out.ensure(f_off + f_ws + 64);
-      e.arena.ensure(ws);
-      uint8_t* const ab = (uint8_t*)e.arena.p;
-      std::vector<HostItem> items(mm);
-      for (size_t k = 0; k < mm; ++k) items[k] = HostItem{jobs[who[from + k]].in, jobs[who[from + k]].in_len, st[k].in_off};
-      const auto staged = upload_staged(e, e.io_in.p, items, w.in_bytes, 4, false);
-      HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), mm * sizeof(BwtStream), hipMemcpyHostToDevice, e.stream));
-      HIP_CHECK(hipMemcpyAsync(ab + o_s2, s2.data(), 4 * mm, hipMemcpyHostToDevice, e.stream));
-      const hipError_t rc = launch_bwt_decode_wide((const uint8_t*)e.io_in.p, (const BwtStream*)(ab + o_st), (const uint32_t*)(ab + o_s2), (uint32_t)mm,
-                                                   (uint32_t)w.tiles, (uint32_t)w.splits, (uint32_t)w.splits2, (uint32_t*)(ab + o_hist), (uint64_t*)ab,
-                                                   ab + o_sp, ab + o_sp2, (uint32_t*)(ab + o_res), (uint8_t*)e.io_out.p, e.stream);
-      if (launch_failed(rc, "device BWT decoder failed: ", note)) { broken = true; return false; }
-      std::vector<uint32_t> res(mm);
-      HIP_CHECK(hipMemcpyAsync(res.data(), ab + o_res, 4 * mm, hipMemcpyDeviceToHost, e.stream));
-      HIP_CHECK(hipStreamSynchronize(e.stream));
-      if (e8) {
-        std::vector<E8Block> fb;
-        std::vector<size_t> fk;
-        std::vector<uint32_t> fst;
-        uint64_t tiles = 0;
-        for (size_t k = 0; k < mm; ++k) {
-          if (res[k] != 0) continue;
-          fb.push_back(E8Block{st[k].out_off, st[k].n, (uint32_t)tiles});
-          fk.push_back(k);
-          tiles += e8_tiles(st[k].n);
-        }
-        if (!une8_run(e, f_off, fb, tiles, ws + f_off + f_ws, fst, note)) { broken = note.find("budget") == std::string::npos; return false; }
-        for (size_t q = 0; q < fb.size(); ++q) if (fst[q] != 0) res[fk[q]] = 1u;
-      }
-      for (size_t k = 0; k < mm; ++k) {
-        StreamJob& j = jobs[who[from + k]];
-        if (res[k] != 0) { j.out_len = 0; continue; }
-        deliver(e, j, st[k].out_off, st[k].n);
-      }
-      HIP_CHECK(hipStreamSynchronize(e.stream));
-      for (size_t k = 0; k < mm; ++k) if (res[k] == 0) jobs[who[from + k]].status = 0;
-      return true;
-    };
     for (size_t from = 0; from < m;) {
-      size_t end = bwt_wide_cut(ns.data(), m, from, 1ull << 31, held_limit, e8);
-      bool ok = end > from;
-      if (!ok) { note = "decoder workspace exceeds the device budget"; end = from + 1; }
-      else ok = run(from, end);
-      if (ok) some = true;
-      else { left = true; for (size_t k = from; k < end; ++k) jobs[who[k]].out_len = 0; }
+      size_t end = bwt_wide_cut(a.n.data(), m, from, 1ull << 31, held_limit, e8);
+      int ran = kBwtOver;
+      if (end == from) { note = "decoder workspace exceeds the device budget"; end = from + 1; }
+      else ran = bwt_run(e, true, e8, jobs, a.who.data() + from, bwt_place(a, from, end, e8), note);
+      if (ran == kBwtRan) some = true;
+      else { left = true; for (size_t k = from; k < end; ++k) jobs[a.who[k]].out_len = 0; }
       from = end;
-      if (broken) {                                     // only a sub-batch beyond the budget lets the next one run
-        for (size_t k = from; k < m; ++k) jobs[who[k]].out_len = 0;
+      if (ran == kBwtBroken) {                          // only a sub-batch beyond the budget lets the next one run
+        for (size_t k = from; k < m; ++k) jobs[a.who[k]].out_len = 0;
         break;
       }
     }
   }
   if (left && !some) return declined(jobs);
-  for (size_t i = 0; i < n; ++i) if (empty[i]) { if (jobs[i].vec) jobs[i].vec->clear(); jobs[i].status = 0; }
-  return 1;
+  return bwt_done(jobs, a);
 }
 int engine_bwt_decode_wide(U32 mbits, bool e8, std::vector<StreamJob>& jobs, std::string& note) { return bwt_decode_wide_batch(mbits, jobs, note, e8); }
 
@@ -464,13 +427,12 @@ int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<S
   if (!n) return 1;
   for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
   if (n > 65535 || kind != 4) { note = "batch outside the device filter's range"; return -1; }
-  std::vector<E8Block> fb(n);
-  uint64_t room = 0, tiles = 0;
+  E8List fl;                                        // every stream is a block: fl.blk[i] is jobs[i]
+  uint64_t room = 0;
   bool fits = true;
   for (size_t i = 0; i < n; ++i) {
-    fb[i] = E8Block{room, jobs[i].in_len, (uint32_t)tiles};
+    fl.add(i, room, jobs[i].in_len);
     room += e8_room(jobs[i].in_len);
-    tiles += e8_tiles(jobs[i].in_len);
     jobs[i].out_len = jobs[i].in_len;
     if (!jobs[i].vec && jobs[i].in_len > jobs[i].cap) fits = false;
   }
@@ -478,21 +440,21 @@ int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<S
   if (!fits) return 0;
   EngineCall call;
   Engine& e = call.e;
-  const uint64_t f_off = align_up(room, 256), f_ws = une8_ws(n, tiles).bytes;
+  const uint64_t f_off = align_up(room, 256), f_ws = fl.ws_bytes();
   if (f_off + f_ws + (1u << 20) > e.budget) { note = "the blocks exceed the device budget"; return declined(jobs); }
   e.io_out.ensure(f_off + f_ws + 64);
   std::vector<HostItem> items(n);
-  for (size_t i = 0; i < n; ++i) items[i] = HostItem{jobs[i].in, jobs[i].in_len, fb[i].off};
+  for (size_t i = 0; i < n; ++i) items[i] = HostItem{jobs[i].in, jobs[i].in_len, fl.blk[i].off};
   const auto staged = upload_staged(e, e.io_out.p, items, room, kE8Lane, false);      // (the rooms: e8_room rounds up to a lane's bytes)
-  std::vector<uint32_t> fst;
-  if (!une8_run(e, f_off, fb, tiles, f_off + f_ws, fst, note)) return declined(jobs);
+  std::vector<char> lost;
+  if (!fl.run(e, f_off, f_off + f_ws, n, lost, note)) return declined(jobs);
   for (size_t i = 0; i < n; ++i) {
     StreamJob& j = jobs[i];
-    if (fst[i] != 0) { j.out_len = 0; continue; }
-    deliver(e, j, fb[i].off, j.in_len);
+    if (lost[i]) { j.out_len = 0; continue; }
+    deliver(e, j, fl.blk[i].off, j.in_len);
   }
   HIP_CHECK(hipStreamSynchronize(e.stream));
-  for (size_t i = 0; i < n; ++i) if (fst[i] == 0) jobs[i].status = 0;
+  for (size_t i = 0; i < n; ++i) if (!lost[i]) jobs[i].status = 0;
   return 1;
 }
 

@@ -287,8 +287,9 @@ static inline bool bwt_wide_stream_admitted(const uint8_t* s, uint64_t len, uint
   idx = i;
   return true;
 }
-// What a batch of wide streams holds on the device: the engine and the emulator's driver add up and place a batch with this.
-struct BwtWideNeed {
+// What a batch of streams of either form holds on the device and where each stream lies in it: the engine and the emulator's
+// driver place a batch with this and with nothing else.
+struct BwtNeed {
   uint64_t streams = 0, in_bytes = 0, nodes = 0, tiles = 0, splits = 0, splits2 = 0, room = 0;
   void add(uint32_t n, bool e8) {
     ++streams;
@@ -299,19 +300,27 @@ struct BwtWideNeed {
     splits2 += bwt_splitters2(n);
     room += e8 ? (((uint64_t)n + 15u) & ~15ull) : n;           // (e8_room: the filter's blocks start on a lane's 16 bytes)
   }
-  // the bytes counted against the budget: the node words, 1 KiB per tile, the two splitter tables, the tables per stream, the
-  // streams and the outputs (each array starts on 256 bytes)
+  // the next stream of the batch, behind those added so far; sp2_off: where its second-level table starts (the wide form's)
+  BwtStream place(uint32_t n, uint32_t idx, bool e8, uint32_t* sp2_off = nullptr) {
+    const BwtStream S = {in_bytes, nodes, room, n, idx, (uint32_t)tiles, (uint32_t)splits};
+    if (sp2_off) *sp2_off = (uint32_t)splits2;
+    add(n, e8);
+    return S;
+  }
+  // the bytes of a wide batch counted against the budget: the node words, 1 KiB per tile, the two splitter tables, the tables per
+  // stream, the streams and the outputs (each array starts on 256 bytes)
   uint64_t bytes() const {
     return 8u * nodes + 1024u * tiles + 16u * splits + 16u * splits2 + streams * (sizeof(BwtStream) + 8u) + in_bytes + room + 8u * 256u;
   }
 };
+typedef BwtNeed BwtWideNeed;       // (its name while only the wide form placed with it)
 // The sub-batch that starts at admitted stream `from` (n[k]: its bytes): consecutive streams while the outputs stay within
 // out_limit and what the batch holds within held_limit.  Returns its end; `from` itself: that stream does not fit alone.
 static inline size_t bwt_wide_cut(const uint32_t* n, size_t m, size_t from, uint64_t out_limit, uint64_t held_limit, bool e8) {
-  BwtWideNeed w;
+  BwtNeed w;
   size_t k = from;
   for (; k < m && k - from < 65535u; ++k) {
-    BwtWideNeed t = w;
+    BwtNeed t = w;
     t.add(n[k], e8);
     if (t.room > out_limit || t.bytes() > held_limit) break;
     w = t;

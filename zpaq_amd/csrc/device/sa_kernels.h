@@ -78,9 +78,9 @@ hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, ui
 hipError_t launch_bwt_decode(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t ntiles, uint32_t nsplit, uint32_t* hist,
                              uint32_t* link, void* splitters, uint32_t* status, uint8_t* out_all, hipStream_t st);
 // ... of blocks of 16 MiB and more (device/bwt_decode_wide_kernel.h): the same for streams admitted by bwt_wide_stream_admitted --
-// 8 bytes per node in link, and nsplit2 entries of 16 bytes in splitters2, stream b's from sp2_off[b] (bwt_splitters2(n) each):
-// the scan takes four parts of a stream's tiles at once, and the splitter list is ranked over its own splitters instead of walked
-// by one lane.
+// 8 bytes per node in link, and nsplit2 entries of 16 bytes in splitters2, stream b's from sp2_off[b] (bwt_splitters2(n) each).
+// Count, link, rank and emit are the bodies above (the last three over BwtNode64); the scan takes four parts of a stream's tiles
+// at once, and the splitter list is ranked over its own splitters instead of walked by one lane.
 hipError_t launch_bwt_decode_wide(const uint8_t* in_all, const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t ntiles,
                                   uint32_t nsplit, uint32_t nsplit2, uint32_t* hist, uint64_t* link, void* splitters, void* splitters2, uint32_t* status,
                                   uint8_t* out_all, hipStream_t st);

@@ -149,14 +149,15 @@ __global__ __launch_bounds__(256) void unbwt_emit_kernel(const BwtStream* stream
   unbwt_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
 }
 
-// device/bwt_decode_wide_kernel.h: the stages that differ for blocks of 16 MiB and more (the count is the small form's)
+// device/bwt_decode_wide_kernel.h: blocks of 16 MiB and more (the count is the small form's; link, rank and emit are its bodies over
+// 8-byte words)
 __global__ __launch_bounds__(1024) void unbwt_wide_scan_kernel(const BwtStream* streams, uint32_t* hist) { unbwt_wide_scan_body(streams, hist); }
 __global__ __launch_bounds__(64) void unbwt_wide_link_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, const uint32_t* hist,
                                                              uint64_t* link) {
-  unbwt_wide_link_body(in_all, streams, nstreams, hist, link);
+  unbwt_link_body(in_all, streams, nstreams, hist, link);
 }
 __global__ __launch_bounds__(256) void unbwt_wide_rank_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link, uint4* sp) {
-  unbwt_wide_rank_body(streams, nstreams, nsplit, link, sp);
+  unbwt_rank_body(streams, nstreams, nsplit, link, sp);
 }
 __global__ __launch_bounds__(256) void unbwt_wide_rank2_kernel(const BwtStream* streams, const uint32_t* sp2_off, uint32_t nstreams, uint32_t nsplit2,
                                                                const uint4* sp, uint4* sp2) {
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void unbwt_wide_offsets1_kernel(const BwtStrea
 }
 __global__ __launch_bounds__(256) void unbwt_wide_emit_kernel(const BwtStream* streams, uint32_t nstreams, uint32_t nsplit, const uint64_t* link,
                                                               const uint4* sp, const uint32_t* status, uint8_t* out_all) {
-  unbwt_wide_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
+  unbwt_emit_body(streams, nstreams, nsplit, link, sp, status, out_all);
 }
 
 __global__ __launch_bounds__(256) void une8_mark_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt,
