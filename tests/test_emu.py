@@ -11,11 +11,11 @@ import pytest
 from conftest import b64, gen_input
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import emu  # noqa: E402
+from model_edge_cases import DEEP_ISSE, MATCH_RING_CFG, PIPE_STRESS_CFG, match_ring_inputs, stress_inputs  # noqa: E402
 
 from zpaq_amd import corpus  # noqa: E402
-
-DEEP_ISSE = "x0,0ci1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1m"
 
 
 def _check(oracle, header, datas, waves):
@@ -259,51 +259,13 @@ def test_pipe_encoder_every_component_type_and_legacy_models(oracle, golden):
     assert len(seen) >= 6
 
 
-PIPE_STRESS_CFG = """
-comp 3 8 0 0 9
-  0 icm 1
-  1 isse 2 0
-  2 cm 9 255
-  3 cm 10 8
-  4 match 8 10
-  5 mix2 8 0 1 24 255
-  6 mix 8 0 6 24 255
-  7 sse 8 6 32 255
-  8 mix2 9 7 6 16 255
-hcomp
-  c++ *c=a b=c
-  d= 0 *d=a
-  d++ a=*b a>>= 1 *d=a
-  d++ a=*b a<<= 1 *d=a
-  d++ b-- a=*b a+=*c *d=a
-  d++ hash *d=a
-  d++ a=*c a>>= 6 *d=a
-  d++ a=*c a>>= 2 *d=a
-  d++ a=*c a>>= 3 *d=a
-  d++ a=*c a<<= 1 *d=a
-  halt
-end
-"""
-
-
 def test_pipe_encoder_table_fetches_that_alias(zlib_, oracle):
     """The units fetch the next bytes' table words before they store this byte's.  Tiny tables and contexts that
     move by little from byte to byte take every aliasing path: same context (forwarding by bit position / from the lane's
     own history), contexts closer than the address range of a byte (fetch after the stores: the bit-lane units' lanes meet
     in memory there), hash rows sharing a 64-byte line.  Both shapes of the encoder."""
     header, _ = zlib_.assemble(PIPE_STRESS_CFG)
-    r = np.random.default_rng(1)
-    walk = (np.cumsum(r.integers(-3, 4, 700)) & 255).astype(np.uint8).tobytes()
-    datas = [walk, corpus.block("text", 600, 5).tobytes(), bytes(500), bytes([7, 7, 8, 8] * 150),
-             corpus.block("lcg", 300, 9).tobytes(), bytes(range(256)) * 2]
-    # MATCH: long matches, a history buffer (1 KiB here) that wraps, candidates overlapping the byte being written
-    rep = bytes(np.random.default_rng(5).integers(0, 256, 97, dtype=np.uint8)) * 40
-    more = [rep, corpus.block("text", 1500, 3).tobytes() * 3, bytes(3000), b"abcabcabd" * 400, corpus.block("records", 4000, 8).tobytes()]
-    # ... and blocks that FIT the history buffer (MATCH then reads its history from the input: pipe_match_in): long and
-    # short repeats, runs of one byte from the block's start on (the reference compares with its zero-filled buffer there),
-    # matches that reach back to the first bytes, a match running across chunk boundaries
-    fit = [rep[:1000], bytes(1000), b"abcabcabd" * 100, corpus.block("text", 1000, 3).tobytes(), bytes([0, 0, 0, 5]) * 200,
-           corpus.block("text", 300, 9).tobytes() * 3, b"\1" * 700, bytes(range(40)) * 20]
+    datas, more, fit = stress_inputs()          # (tests/model_edge_cases.py: what each of the three sets is for)
     for mode in (0, 1):
         _pipe_check(oracle, header, [b"\0" + d for d in datas], chunk=64, mode=mode)
         _pipe_check(oracle, header, [b"\0" + d for d in more], chunk=256, mode=mode)
@@ -322,15 +284,6 @@ def test_coder_normalisation_in_closed_form(tmp_path):
     assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout[-500:]
 
 
-MATCH_RING_CFG = """
-comp 2 0 0 0 1
-  0 match 10 9
-hcomp
-  b=a a=*d a<<= 8 a+=b *d=a halt
-end
-"""
-
-
 def test_match_unit_near_the_end_of_its_history_ring(zlib_, oracle):
     """update0 compares backwards from a candidate with indices modulo the buffer size (libzpaq.cpp:1995-1998): behind a
     candidate near the block's start that is the END of the ring, zero only while nothing has been written there.  A block
@@ -338,17 +291,7 @@ def test_match_unit_near_the_end_of_its_history_ring(zlib_, oracle):
     (pipe_match_any; the advisor's case of round 5: 508 bytes against a 512-byte buffer, a zero run near the end, the bytes
     that follow the block's first bytes repeated behind it).  Lengths around both thresholds, every launch form."""
     header, _ = zlib_.assemble(MATCH_RING_CFG)
-    Y, X = 0x59, 0x58
-
-    def case(n):
-        d = bytearray(np.random.default_rng(n).integers(1, 256, n, dtype=np.uint8).tobytes())
-        d[1:3] = bytes([Y, X])
-        d[n - 24] = X
-        d[n - 23:n - 10] = bytes(13)
-        d[n - 10:n - 8] = bytes([Y, X])
-        return bytes(d)
-
-    datas = [case(n) for n in (508, 512, 300, 258, 257, 256, 511, 400)]
+    datas = match_ring_inputs()
     for mode in (0, 1):
         _pipe_check(oracle, header, datas, chunk=64, mode=mode)
     _pipe_check(oracle, header, datas, chunk=64, mode=0, persist=True)

@@ -492,6 +492,16 @@ constexpr int team_mix2_slot(int i) {
   return s;
 }
 constexpr bool mix2_pf(const CompK& c) { return c.a5 == 255u && c.mask0 >= 255u; }
+// A CM below 512 words takes its word AFTER the last bit's store, not from the candidates fetched before it: the
+// words of a byte are not distinct there.  Chain::ANY_NONPF_GL says so for tables of 2 .. 511 words only -- the
+// other decoders keep a table of ONE word in a register (`resident`) -- so here the one-word CM counts as well:
+// its candidates are the word itself, read a bit too early.
+template <class Chain>
+constexpr bool team_cm_reread() {
+  bool one_word = false;
+  for (int i = 0; i < Chain::N; ++i) one_word = one_word || (Chain::comp[i].type == C_CM && Chain::comp[i].mask0 == 0u);
+  return Chain::ANY_NONPF_GL || one_word;
+}
 
 typedef unsigned long long __attribute__((aligned(1))) team_u64u;
 typedef __attribute__((address_space(1))) const team_u64u g_u64u;
@@ -671,7 +681,7 @@ __device__ __forceinline__ void team_mixers(const TT& T, lds_u8* const lds0, con
           m2w[k2] = ylast ? m2c1[k2] : m2c0[k2];
         }
       });
-      if constexpr (Chain::ANY_NONPF_GL) {
+      if constexpr (team_cm_reread<Chain>()) {
         if (is_cm && !pf_lane) gw = G32(goff + 4u * gidx);
       }
     } else {
@@ -1381,7 +1391,7 @@ __device__ __forceinline__ void team_tail(const TT& T, lds_u8* const lds0, const
     gidx = (h ^ (unsigned)hmap4) & gmask;
     if constexpr (pf_now) {
       gw = ylast ? gwc1 : gwc0;
-      if constexpr (Chain::ANY_NONPF_GL) {
+      if constexpr (team_cm_reread<Chain>()) {
         if (is_cm && !pf_lane) gw = G32(goff + 4u * gidx);
       }
     } else {
