@@ -257,6 +257,9 @@ class Oracle:
         L.zo_decode.restype = C.c_longlong
         L.zo_decode.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, _u8p, C.c_size_t,
                                 C.POINTER(C.c_size_t)]
+        L.zo_decode_limit.restype = C.c_int
+        L.zo_decode_limit.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, _u8p, C.c_size_t,
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.zo_hcomp_trace.restype = C.c_int
         L.zo_hcomp_trace.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.zo_model_new.restype = C.c_void_p
@@ -325,6 +328,19 @@ class Oracle:
         if r < 0:
             raise RuntimeError(f"zo_decode failed: {r}")
         return 0, out[:min(r, out.size)].tobytes()
+
+    def decode_limited(self, header, coded, max_out):
+        """zpq_decode_batch's contract for one modelled block, valid or not -> (status, bytes, consumed): status 0 at the end
+        of the stream (consumed = bytes read, marker included) or at the capacity (consumed = 0); 2 / 6 / 5 as
+        decode_outcome and for HCOMP's `error`, with the bytes that were complete before it (zo_decode_limit)."""
+        h = _bytes_arr(header)
+        c = _bytes_arr(coded)
+        out = np.empty(max(int(max_out), 1), np.uint8)
+        n, used = C.c_size_t(0), C.c_size_t(0)
+        st = self.lib.zo_decode_limit(_ptr(h), h.size, _ptr(c), c.size, _ptr(out), int(max_out), C.byref(n), C.byref(used))
+        if st in (1, 4):
+            raise RuntimeError(f"zo_decode_limit failed: {st}")
+        return int(st), out[:n.value].tobytes(), int(used.value)
 
     def hcomp_trace(self, header, data, ncomp) -> np.ndarray:
         h = _bytes_arr(header)

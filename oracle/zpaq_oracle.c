@@ -683,6 +683,62 @@ done:
   return ret;
 }
 
+/* Decoder::decode / decompress (libzpaq.cpp:2104-2145) under zpq_decode_batch's contract (include/zpaq_amd.h): a capacity,
+ * and on an error the bytes that were complete before it.
+ * Known difference: Decoder::decompress re-reads four bytes whenever curr == 0 at a byte boundary (2129), not only at the
+ * start of a segment.  A searched-for stream gets there (a shift that takes low to 0, then to 1, with 00 shifted into a curr
+ * whose low 24 bits are zero, at the last bit of a byte; about 2^-24 per bit); this function, like every device decoder,
+ * reports status 2 on the next bit instead. */
+int zo_decode_limit(const uint8_t* header, size_t hlen, const uint8_t* coded, size_t ncoded,
+                    uint8_t* out, size_t max_out, size_t* out_len, size_t* consumed) {
+  int err = 0;
+  size_t rp = 0, n = 0;
+  *out_len = 0;
+  *consumed = 0;
+  if (hlen < 7 || header[6] == 0) return 4;                /* modelled blocks only */
+  zo_model* m = zo_model_new(header, hlen, &err);
+  if (!m) return err == ZO_ENOMEM ? 1 : 4;
+  U32 low = 1, high = 0xFFFFFFFFu, curr = 0;
+  int status = 0;
+  for (int i = 0; i < 4; ++i) {
+    if (rp >= ncoded) { status = 6; goto done; }
+    curr = curr << 8 | coded[rp++];
+  }
+  for (;;) {
+    if (n == max_out) goto done;                          /* the capacity: status 0, consumed 0 */
+    int c = 1;
+    for (int b = -1; b < 8; ++b) {                        /* b == -1: the end-of-stream flag, decode(0) */
+      U32 p = 0;
+      if (b >= 0) p = (U32)zo_predict(m) * 2 + 1;
+      if (curr < low || curr > high) { status = 2; goto done; }
+      U32 mid = low + (U32)(((U64)(high - low) * p) >> 16);
+      int y;
+      if (curr <= mid) { y = 1; high = mid; } else { y = 0; low = mid + 1; }
+      while ((high ^ low) < 0x1000000u) {
+        high = high << 8 | 255;
+        low = low << 8;
+        low += (low == 0);
+        if (rp >= ncoded) { status = 6; goto done; }
+        curr = curr << 8 | coded[rp++];
+      }
+      if (b < 0) {
+        if (y) {
+          if (curr != 0) status = 2; else *consumed = rp;
+          goto done;
+        }
+      } else {
+        c += c + y;
+        if (zo_update(m, y) < 0) { status = 5; goto done; }   /* HCOMP's error, inside the last bit's update (2142) */
+      }
+    }
+    out[n++] = (U8)(c - 256);
+  }
+done:
+  zo_model_free(m);
+  *out_len = n;
+  return status;
+}
+
 int zo_hcomp_trace(const uint8_t* header, size_t hlen, const uint8_t* in, size_t n, uint32_t* hout) {
   int err = 0;
   zo_model* m = zo_model_new(header, hlen, &err);

@@ -172,10 +172,10 @@ def build_team(header: bytes):
     return exe, team_threads(src)
 
 
-def run(header: bytes, inputs: Sequence[bytes], decode: bool = False, waves: int = 4, out_cap: int | None = None, dual: bool = False,
-        team: bool = False):
+def run(header: bytes, inputs: Sequence[bytes], decode: bool = False, waves: int = 4, out_cap: int | Sequence[int] | None = None,
+        dual: bool = False, team: bool = False):
     """Code every input as one block (one wavefront each; dual: the decoder with two blocks per wavefront; team: the
-    lockstep decoder).  Returns [(bytes, status, consumed)]."""
+    lockstep decoder).  out_cap: one capacity for all blocks, or one per block.  Returns [(bytes, status, consumed)]."""
     if team:
         exe, thr = build_team(header)
         waves, dual = thr // 64, False
@@ -190,6 +190,10 @@ def run(header: bytes, inputs: Sequence[bytes], decode: bool = False, waves: int
             p = os.path.join(td, f"in{i}")
             open(p, "wb").write(bytes(d))
             paths.append(p)
+        if not isinstance(cap, int):
+            assert len(cap) == len(inputs)
+            open(os.path.join(td, "caps"), "w").write("".join("%d\n" % c for c in cap))
+            cap = "@" + os.path.join(td, "caps")
         r = subprocess.run([exe, "dec3" if team else ("dec2" if dual else ("dec" if decode else "enc")), str(waves), hp, str(cap), os.path.join(td, "out"), *paths],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
         if r.returncode != 0:

@@ -3,6 +3,7 @@
 //   emu_run enc|dec <waves> <header.bin> <out_cap> <out_prefix> <input> [<input> ...]
 //
 // <waves> = wavefronts (= blocks) per workgroup the kernel was generated for.
+// <out_cap> = one capacity for every block, or @<file>: a capacity per block, one number per line.
 //
 // Runs the generated specialised kernel (compiled into this executable from the text
 // zpq_plan_spec_source returns) over the given inputs, one ZPAQ block per wavefront,
@@ -101,9 +102,16 @@ int main(int argc, char** argv) {
   const bool dec = dual || !strcmp(argv[1], "dec");
   const unsigned waves = (unsigned)atoi(argv[2]);
   const std::vector<uint8_t> header = slurp(argv[3]);
-  const uint32_t out_cap = (uint32_t)strtoul(argv[4], nullptr, 10);
   const std::string prefix = argv[5];
   const unsigned nb = (unsigned)(argc - 6);
+  std::vector<uint32_t> caps(nb, (uint32_t)strtoul(argv[4], nullptr, 10));
+  if (argv[4][0] == '@') {
+    FILE* f = fopen(argv[4] + 1, "r");
+    if (!f) { perror(argv[4] + 1); return 2; }
+    for (unsigned b = 0; b < nb; ++b)
+      if (fscanf(f, "%u", &caps[b]) != 1) { fprintf(stderr, "emu_run: %s holds fewer than %u capacities\n", argv[4] + 1, nb); return 2; }
+    fclose(f);
+  }
 
   zpq_plan* plan = nullptr;
   if (zpq_plan_create(header.data(), header.size(), &plan) != 0) { fprintf(stderr, "plan: %s\n", zpq_last_error()); return 2; }
@@ -134,6 +142,7 @@ int main(int argc, char** argv) {
   if (!guard && !pool) { fprintf(stderr, "arena pool: out of memory\n"); return 2; }
   for (unsigned b = 0; b < njobs; ++b) {
     if (b < nb) ins[b] = slurp(argv[6 + b]);
+    const uint32_t out_cap = caps[b];
     outs[b].assign((size_t)out_cap + 64, 0xEE);
     uint8_t* const arena = guard ? emu::guard_alloc(ph->arena_bytes, 256, 0) : pool + (size_t)b * ph->arena_bytes;
     init_arena(arena, blob, tb);
@@ -148,7 +157,7 @@ int main(int argc, char** argv) {
     }
     jobs[b].out = outs[b].data();
     jobs[b].in_len = (uint32_t)ins[b].size();
-    jobs[b].out_cap = b < nb ? out_cap : 0;
+    jobs[b].out_cap = out_cap;
     jobs[b].res_slot = b;
     res[b] = zpq::BlockResult{0, 0, -1, 0};
   }
@@ -156,6 +165,7 @@ int main(int argc, char** argv) {
   const unsigned per_wg = dual ? 8 : waves;      // blocks per workgroup
   for (unsigned wg = 0; wg < (nb + per_wg - 1) / per_wg; ++wg) emu::run_workgroup(kernel_thunk, &l, team ? 64 * waves : (dual ? 256 : 64 * waves), wg);
   for (unsigned b = 0; b < nb; ++b) {
+    const uint32_t out_cap = caps[b];
     // guard bytes past the capacity must be untouched
     for (unsigned k = 0; k < 64; ++k)
       if (outs[b][(size_t)out_cap + k] != 0xEE) { fprintf(stderr, "block %u wrote past its output capacity\n", b); return 3; }

@@ -218,10 +218,13 @@ def test_decoder_status_codes(gpu, golden, oracle):
         outcomes.append(oracle.decode_outcome(hdr, bytes(bad), len(d) + 64))
     damaged.append(good[:-6]); outcomes.append(oracle.decode_outcome(hdr, good[:-6], len(d) + 64))
     res, st = gpu.decode_batch([plan] * len(damaged), damaged, [len(d) + 64] * len(damaged), check=False)
-    for (dec, _), got, (want_st, want) in zip(res, st, outcomes):
+    for bad, (dec, used), got, (want_st, want) in zip(damaged, res, st, outcomes):
         assert got == want_st, (got, want_st)
         if want_st == 0:
             assert dec == want
+        # ... and the bytes decoded before an error, and the bytes consumed at status 0 (zo_decode_limit)
+        lim = oracle.decode_limited(hdr, bad, len(d) + 64)
+        assert (got, dec) == lim[:2] and (got != 0 or used == lim[2]), (got, len(dec), used, lim[0], len(lim[1]), lim[2])
     assert {o[0] for o in outcomes} >= {2}, outcomes      # the sample does contain detected corruption
     # output overflow on encode is reported, not silently truncated
     outs, st, lens = gpu.encode_batch([plan], [b"\0" + d], out_cap=[100], check=False)
