@@ -393,6 +393,31 @@ int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, co
  * groups of 256 segments and more, the smallest batch at which it was faster than both other routes.  Any set
  * value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  The bytes are the same either way. */
 uint32_t zpq_last_device_unlz_segments(void);
+/* The same batch through the decoder for LONG streams (device/lz77_decode_wide_kernel.h): a stream is parsed in
+ * pieces of 16 KiB from provisional starts, a wavefront each; one wavefront per stream stitches the pieces' lists along the true
+ * walk (the code stream re-synchronises by itself); the checks that need the absolute output position follow, a lane per token;
+ * and the copy is pointer jumping over a word per output byte, no lane waiting for another.  The argument list, the status
+ * meanings and the contract per stream are zpq_lz77_decode_device's; a stream of any length is taken, a short one too.  Range:
+ * 65 535 streams, outputs below 2^31 bytes per stream and per batch; 36 bytes per stream byte (rounded up to whole pieces), 4
+ * bytes per output byte, the streams and the outputs within the device budget.  ZPQ_E_OVERFLOW with every size reported and
+ * nothing written when a decoded block does not fit its buffer; ZPQ_E_UNSUPPORTED with a note without a device, for another
+ * kind of method, or outside the range.  ZPAQ_AMD_UNLZ_WIDE_PIECE=<bytes>, read per call, overrides the piece size (clamped to
+ * [64, 2^20], rounded up to a multiple of 64: tests). */
+int zpq_lz77_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                                uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that went that way.  Inside a group that qualifies for
+ * zpq_last_device_unlz_segments' route, the segments whose stream has at least ZPAQ_AMD_UNLZ_WIDE_FROM bytes (default 1 MiB; read
+ * per call: tests) are candidates; ZPAQ_AMD_DEVICE_UNLZ_WIDE=0|1 forces the route off or on for them.  Unset it is off: it is
+ * taken only from a measured stream size at which it beat both other routes on every kind of data, and the measurement is not
+ * complete yet (DESIGN 4.5.10 has the table of what was timed).  What it declines, and the rest of the group, goes on exactly as without it, ZPAQ_AMD_DEVICE_UNLZ included.
+ * Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0; E8E9 groups never qualify.  The bytes are the same
+ * either way. */
+uint32_t zpq_last_device_unlz_wide_segments(void);
+/* Of this process's last call of that decoder (zpq_lz77_decode_device_wide, or the route of zpq_decompress): pieces; pieces whose
+ * list was adopted in the state the true walk entered them in; pieces met after a serial stretch; pieces walked serially to their
+ * end (the rest: a code leapt over them) -- and the jump rounds of its longest copy. */
+void zpq_last_unlz_wide_pieces(uint32_t out4[4]);
+uint32_t zpq_last_unlz_wide_rounds(void);
 /* The same for a batch of BWT streams (level 3 without E8E9, args[0] <= 4: x0,3 .. x4,3) on the device
  * (device/bwt_decode_kernel.h: a stable counting sort per tile, then the list ranked from every 256th node at once).  A stream
  * is S[0 .. n] and idx in 4 bytes, low byte first.  status[b]: 0 decoded -- out[b] holds, byte for byte, what

@@ -89,6 +89,13 @@ def lib():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_last_device_unlz_segments.restype = C.c_uint32
     L.zpq_last_device_unlz_segments.argtypes = []
+    L.zpq_lz77_decode_device_wide.argtypes = L.zpq_lz77_decode_device.argtypes
+    L.zpq_last_device_unlz_wide_segments.restype = C.c_uint32
+    L.zpq_last_device_unlz_wide_segments.argtypes = []
+    L.zpq_last_unlz_wide_pieces.restype = None
+    L.zpq_last_unlz_wide_pieces.argtypes = [C.POINTER(C.c_uint32)]
+    L.zpq_last_unlz_wide_rounds.restype = C.c_uint32
+    L.zpq_last_unlz_wide_rounds.argtypes = []
     L.zpq_bwt_decode_device.argtypes = [C.c_char_p, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_bwt_decode_device_wide.argtypes = L.zpq_bwt_decode_device.argtypes
@@ -416,8 +423,9 @@ def postprocess_block(xmethod: str, stream, cap: Optional[int] = None):
     return rc, (out[:size].tobytes() if rc == 0 else b""), size
 
 
-def lz77_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
-    """zpq_lz77_decode_device: a batch of LZ77 streams (level 1 / 2, no E8E9) back into their blocks on the device.
+def lz77_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0, wide: bool = False):
+    """zpq_lz77_decode_device: a batch of LZ77 streams (level 1 / 2, no E8E9) back into their blocks on the device
+    (wide: zpq_lz77_decode_device_wide, the decoder that parses a stream in pieces).
     caps = the output capacities; `guard` bytes of `fill` lie behind each.  Returns (return code, buffers -- cap + guard bytes each,
     as the call left them --, sizes, statuses: 0 decoded, 1 declined)."""
     n = len(streams)
@@ -430,8 +438,31 @@ def lz77_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], gua
     OC = (C.c_size_t * n)(*caps)
     OL = (C.c_size_t * n)()
     ST = (C.c_int32 * n)()
-    rc = lib().zpq_lz77_decode_device(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
+    entry = lib().zpq_lz77_decode_device_wide if wide else lib().zpq_lz77_decode_device
+    rc = entry(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
     return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
+
+
+def lz77_decode_device_wide(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
+    """zpq_lz77_decode_device_wide: lz77_decode_device through the decoder for long streams (ZPAQ_AMD_UNLZ_WIDE_PIECE sets the piece)."""
+    return lz77_decode_device(xmethod, streams, caps, guard, fill, wide=True)
+
+
+def last_device_unlz_wide_segments() -> int:
+    """Segments of the last decompress call that the device's LZ77 decoder for long streams decoded (ZPAQ_AMD_DEVICE_UNLZ_WIDE)."""
+    return int(lib().zpq_last_device_unlz_wide_segments())
+
+
+def last_unlz_wide_pieces() -> Tuple[int, int, int, int]:
+    """Of this process's last call of that decoder: pieces, adopted as entered, met after a serial stretch, walked to their end."""
+    out = (C.c_uint32 * 4)()
+    lib().zpq_last_unlz_wide_pieces(out)
+    return tuple(int(x) for x in out)
+
+
+def last_unlz_wide_rounds() -> int:
+    """Jump rounds of the longest copy of this process's last call of that decoder."""
+    return int(lib().zpq_last_unlz_wide_rounds())
 
 
 def last_device_unlz_segments() -> int:

@@ -761,6 +761,23 @@ int zpq_lz77_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_unlz_segments(void) { return last_device_unlz_segments(); }
 
+// ... LZ77 streams parsed in pieces (device/lz77_decode_wide_kernel.h)
+int zpq_lz77_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                                size_t* outlen, int32_t* status) {
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        const int level = args[1] & 3;
+        return xm[0] == '0' || args[1] < 1 || args[1] > 3 || level < 1 || level > 2 ? "not an LZ77 method of level 1 or 2 without E8E9" : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) {
+        return engine_lz77_decode_wide((U32)(args[1] & 3), lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+      });
+}
+
+uint32_t zpq_last_device_unlz_wide_segments(void) { return last_device_unlz_wide_segments(); }
+void zpq_last_unlz_wide_pieces(uint32_t out4[4]) { if (out4) engine_last_unlz_wide_pieces(out4); }
+uint32_t zpq_last_unlz_wide_rounds(void) { return engine_last_unlz_wide_rounds(); }
+
 // ... BWT streams (device/bwt_decode_kernel.h)
 int zpq_bwt_decode_device(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                           size_t* outlen, int32_t* status) {

@@ -166,6 +166,25 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
 // it was faster than both other routes (the translated program on the device, a lane per segment; the host's translated
 // programs) in every alternation of the measurement -- 256 segments of 1 MiB (DESIGN 4.5.3 has the table and the rule).
 inline bool lz_unlz_pays(U64 segments, U64 /*stream_bytes*/) { return segments >= 256; }
+// The same streams through the decoder that parses a stream in pieces and copies by pointer jumping (device/lz77_decode_wide_kernel.h,
+// DESIGN 4.5.10), for streams long enough to be cut: the same contract per stream, 1 / 0 / -1 as StreamJob says.  The pieces'
+// tokens, the final list and the start states (36 bytes per stream byte, rounded up to whole pieces), 4 bytes per output byte, the
+// streams and the outputs count against the engine's budget; at most 65 535 streams, outputs below 2^31 bytes.  Jobs that all
+// deliver into vectors are cut into sub-batches that fit, and only a stream that does not fit alone is declined (status 1; -1 +
+// note when nothing else was decoded); jobs with buffers of their own run as one batch or are declined (-1 + note).
+// ZPAQ_AMD_UNLZ_WIDE_PIECE=<bytes>, read per call, overrides the piece size (kUnlzWidePiece; clamped to [64, 2^20], rounded up to a
+// multiple of 64: tests).
+int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note);
+// pieces of this process's last engine_lz77_decode_wide call: all, adopted in the state the walk entered them in, met after a
+// serial stretch, walked serially to their end (the rest: a code leapt over them); and the jump rounds of its longest copy
+void engine_last_unlz_wide_pieces(U32 out[4]);
+U32 engine_last_unlz_wide_rounds();
+// Whether the segments of a group whose streams are long enough (host/blocks.cpp: ZPAQ_AMD_UNLZ_WIDE_FROM) take that route when
+// ZPAQ_AMD_DEVICE_UNLZ_WIDE is unset.  The rule is the one of lz_unlz_pays, fixed before the measurement: from the smallest
+// measured stream size at which the route beat both other settings in all three alternations on every kind of data; off, behind
+// the knob only, if the kinds disagree.  Off while the measurement is incomplete, and it is: the 16 MiB class is timed (the route won on text, records and random
+// bytes), the 64 MiB class in part only (DESIGN 4.5.10 has the table).
+inline bool lz_unlz_wide_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
 // BWT streams back into their blocks on the device (device/bwt_decode_kernel.h): what the program of a BWT method without E8E9
 // at args[0] <= 4 (mbits = the program's pm = ph) makes of each stream, or status 1: declined, the output untouched -- a stream
 // outside the rule 1 <= idx <= n, S[idx] == 255 or shorter than 5 bytes, n >= 2^24, n + 257 > 2^mbits, a path that has not n

@@ -252,6 +252,179 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
   return lz77_decode_batch(level, rb, min_match, mbits, jobs, note, false);
 }
 
+// device/lz77_decode_wide_kernel.h for a batch of host streams.  Streams who[0 .. m) of `jobs` as one batch on the
+// device: the upload, the pieces' parses, the stitch and the final lists; 40 bytes per stream back, the counts among them; the outputs
+// placed back to back (sizes first, then emission: no bound is guessed); a word per output byte linked, jumped until a round
+// changes nothing, emitted; the outputs down.  kUnlzwRan: status and out_len of its jobs are final.  kUnlzwShort: some decoded
+// block does not fit its job's buffer -- every out_len is reported, nothing was written.  Otherwise nothing was delivered either
+// and `note` says why -- kUnlzwOver: the batch does not fit the budget or 2 GiB of output; kUnlzwBroken: a launch failed.
+namespace {
+enum { kUnlzwBroken = -1, kUnlzwOver = 0, kUnlzwRan = 1, kUnlzwShort = 2 };
+struct UnlzWideParams { U32 level, rb, min_match, mbits, piece; };
+std::atomic<U32> g_last_unlz_wide_pieces[4], g_last_unlz_wide_rounds{0};
+
+// what a stream holds on the device before its size is known: the slots of three arrays and the stream
+uint64_t unlz_wide_slots(U32 in_len, U32 piece) { return ((uint64_t)in_len + piece - 1) / piece * piece; }
+uint64_t unlz_wide_need(U32 in_len, U32 piece) { return 36 * unlz_wide_slots(in_len, piece) + align_up(in_len, 4) + 256; }
+
+int unlz_wide_run(Engine& e, const UnlzWideParams& P, std::vector<StreamJob>& jobs, const size_t* who, size_t m, U32 counts[4], U32& rounds, std::string& note) {
+  std::vector<UnlzWideStream> st(m);
+  std::vector<UnlzWideRef> refs;
+  uint64_t in_bytes = 0, slots = 0;
+  for (size_t k = 0; k < m; ++k) {
+    UnlzWideStream& S = st[k];
+    memset(&S, 0, sizeof(S));
+    S.in_off = in_bytes;
+    S.tok_off = slots;
+    S.in_len = jobs[who[k]].in_len;
+    S.piece0 = (uint32_t)refs.size();
+    S.npieces = (uint32_t)(unlz_wide_slots(S.in_len, P.piece) / P.piece);
+    S.level = P.level;
+    S.rb = P.rb;
+    S.min_match = P.min_match;
+    S.mbits = P.mbits;
+    for (uint32_t i = 0; i < S.npieces; ++i) refs.push_back(UnlzWideRef{(uint32_t)k, i});
+    in_bytes += align_up(S.in_len, 4);
+    slots += (uint64_t)S.npieces * P.piece;
+  }
+  const size_t np = refs.size();
+  // the arena buffer (idle between batches): the pieces' tokens, the final lists, the start states, the tables
+  Carve cv;
+  cv.take(16 * slots);
+  const uint64_t o_fin = cv.take(16 * slots);
+  const uint64_t o_states = cv.take(4 * slots);
+  const uint64_t o_pieces = cv.take(np * sizeof(UnlzWidePieceOut));
+  const uint64_t o_adopt = cv.take(np * sizeof(UnlzWideAdopt));
+  const uint64_t o_refs = cv.take(np * sizeof(UnlzWideRef));
+  const uint64_t o_st = cv.take(m * sizeof(UnlzWideStream));
+  const uint64_t o_outs = cv.take(m * sizeof(UnlzWideOut));
+  const uint64_t o_place = cv.take(m * sizeof(UnlzWidePlace));
+  const uint64_t o_flags = cv.take(4 * kUnlzWideRounds);
+  const uint64_t ws = cv.at + 256;
+  if (ws + in_bytes + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return kUnlzwOver; }
+  e.io_in.ensure(in_bytes + 64);
+  e.arena.ensure(ws);
+  uint8_t* const ab = (uint8_t*)e.arena.p;
+  std::vector<HostItem> items(m);
+  for (size_t k = 0; k < m; ++k) items[k] = HostItem{jobs[who[k]].in, jobs[who[k]].in_len, st[k].in_off};
+  const auto staged = upload_staged(e, e.io_in.p, items, in_bytes, 4, false);
+  HIP_CHECK(hipMemcpyAsync(ab + o_st, st.data(), m * sizeof(UnlzWideStream), hipMemcpyHostToDevice, e.stream));
+  if (np) HIP_CHECK(hipMemcpyAsync(ab + o_refs, refs.data(), np * sizeof(UnlzWideRef), hipMemcpyHostToDevice, e.stream));
+  const uint8_t* const in_all = (const uint8_t*)e.io_in.p;
+  const UnlzWideStream* const d_st = (const UnlzWideStream*)(ab + o_st);
+  hipError_t rc = launch_unlz_wide_parse(P.level, in_all, d_st, (uint32_t)m, (const UnlzWideRef*)(ab + o_refs), (uint32_t)np, P.piece, ab, (uint32_t*)(ab + o_states),
+                                         (UnlzWidePieceOut*)(ab + o_pieces), ab + o_fin, (UnlzWideAdopt*)(ab + o_adopt), (UnlzWideOut*)(ab + o_outs),
+                                         e.stream);
+  if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return kUnlzwBroken;
+  std::vector<UnlzWideOut> outs(m);
+  HIP_CHECK(hipMemcpyAsync(outs.data(), ab + o_outs, m * sizeof(UnlzWideOut), hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  std::vector<UnlzResult> res(m);
+  std::vector<UnlzWidePlace> place;
+  std::vector<uint64_t> off(m);
+  uint64_t room = 0;
+  bool fits = true;
+  for (size_t k = 0; k < m; ++k) {
+    StreamJob& j = jobs[who[k]];
+    const UnlzWideStats& c = outs[k].stats;
+    res[k] = outs[k].r;
+    if (outs[k].err != ~0ull) res[k].status = (uint32_t)(outs[k].err & 7u);        // the first token that failed a position check
+    counts[0] += c.pieces; counts[1] += c.entered; counts[2] += c.met; counts[3] += c.walked;
+    off[k] = room;
+    if (res[k].status != kUnlzOk) continue;
+    j.out_len = res[k].out_len;
+    if (res[k].out_len) place.push_back(UnlzWidePlace{room, res[k].out_len, res[k].ntok, (uint32_t)k, 0u});
+    room += res[k].out_len;
+    if (!j.vec && res[k].out_len > j.cap) fits = false;
+  }
+  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return kUnlzwOver; }
+  const uint64_t w_off = align_up(room, 256);
+  if (ws + in_bytes + w_off + 4 * room + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; return kUnlzwOver; }
+  if (!fits) return kUnlzwShort;
+  if (room) {
+    e.io_out.ensure(w_off + 4 * room + 64);
+    uint32_t* const w = (uint32_t*)((uint8_t*)e.io_out.p + w_off);
+    uint32_t* const d_flags = (uint32_t*)(ab + o_flags);
+    HIP_CHECK(hipMemcpyAsync(ab + o_place, place.data(), place.size() * sizeof(UnlzWidePlace), hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemsetAsync(d_flags, 0, 4 * kUnlzWideRounds, e.stream));
+    rc = launch_unlz_wide_link(in_all, d_st, (const UnlzWidePlace*)(ab + o_place), (uint32_t)place.size(), (uint32_t)room, ab + o_fin, w, e.stream);
+    if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return kUnlzwBroken;
+    for (uint32_t r = 0;; ++r) {
+      if (r == kUnlzWideRounds) { note = "the copy did not settle within the bound of jump rounds"; return kUnlzwOver; }
+      rc = launch_unlz_wide_jump(w, (uint32_t)room, d_flags + r, e.stream);
+      if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return kUnlzwBroken;
+      uint32_t more = 0;
+      HIP_CHECK(hipMemcpyAsync(&more, d_flags + r, 4, hipMemcpyDeviceToHost, e.stream));
+      HIP_CHECK(hipStreamSynchronize(e.stream));
+      if (r + 1 > rounds) rounds = r + 1;
+      if (!more) break;
+    }
+    rc = launch_unlz_wide_emit(w, (uint32_t)room, (uint8_t*)e.io_out.p, e.stream);
+    if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return kUnlzwBroken;
+  }
+  for (size_t k = 0; k < m; ++k) if (res[k].status == kUnlzOk) deliver(e, jobs[who[k]], off[k], res[k].out_len);
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t k = 0; k < m; ++k) if (res[k].status == kUnlzOk) jobs[who[k]].status = 0;
+  return kUnlzwRan;
+}
+}  // namespace
+
+void engine_last_unlz_wide_pieces(U32 out[4]) { for (int k = 0; k < 4; ++k) out[k] = g_last_unlz_wide_pieces[k].load(std::memory_order_relaxed); }
+U32 engine_last_unlz_wide_rounds() { return g_last_unlz_wide_rounds.load(std::memory_order_relaxed); }
+
+// The batch as one when it fits.  Jobs that all deliver into vectors (an archive's segments) may be cut: consecutive sub-batches
+// by what they hold before their sizes are known, and a sub-batch whose decoded blocks then exceed the budget or 2 GiB runs again
+// stream by stream; only a stream that does not fit alone is declined (status 1; -1 + note when nothing else was decoded).  Jobs
+// with buffers of their own run as one batch or not at all: nothing may be written before every size is known.  After a failed
+// launch nothing more is started.
+int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+  const size_t n = jobs.size();
+  for (int k = 0; k < 4; ++k) g_last_unlz_wide_pieces[k].store(0, std::memory_order_relaxed);
+  g_last_unlz_wide_rounds.store(0, std::memory_order_relaxed);
+  if (!n) return 1;
+  bool all_vec = true;
+  for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; all_vec = all_vec && j.vec; }
+  if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
+  U64 piece = kUnlzWidePiece;
+  if (const char* v = getenv("ZPAQ_AMD_UNLZ_WIDE_PIECE")) { const long long x = atoll(v); if (x > 0) piece = (U64)x; }
+  const UnlzWideParams P{level, rb, min_match, mbits, unlz_wide_piece_clamped(piece)};
+  std::vector<size_t> who(n);
+  for (size_t i = 0; i < n; ++i) who[i] = i;
+  U32 counts[4] = {0, 0, 0, 0}, rounds = 0;
+  bool some = false, left = false, broken = false;
+  EngineCall call;
+  Engine& e = call.e;
+  auto drop = [&](size_t from, size_t end) { left = true; for (size_t i = from; i < end; ++i) { jobs[i].out_len = 0; jobs[i].status = 1; } };
+  for (size_t from = 0; from < n && !broken;) {
+    size_t end = n;
+    if (all_vec) {
+      uint64_t need = 0;
+      for (end = from; end < n; ++end) {
+        need += unlz_wide_need(jobs[end].in_len, P.piece);
+        if (end > from && need > e.budget / 2) break;
+      }
+    }
+    int ran = unlz_wide_run(e, P, jobs, who.data() + from, end - from, counts, rounds, note);
+    if (ran == kUnlzwShort) return 0;                       // (one batch: nothing was written)
+    if (ran == kUnlzwOver && all_vec && end - from > 1) {
+      for (size_t i = from; i < end && !broken; ++i) {
+        ran = unlz_wide_run(e, P, jobs, who.data() + i, 1, counts, rounds, note);
+        if (ran == kUnlzwRan) some = true; else drop(i, i + 1);
+        if (ran == kUnlzwBroken) { broken = true; drop(i + 1, n); }
+      }
+    } else if (ran == kUnlzwRan) some = true;
+    else {
+      drop(from, end);
+      if (ran == kUnlzwBroken) { broken = true; drop(end, n); }
+    }
+    from = end;
+  }
+  for (int k = 0; k < 4; ++k) g_last_unlz_wide_pieces[k].store(counts[k], std::memory_order_relaxed);
+  g_last_unlz_wide_rounds.store(rounds, std::memory_order_relaxed);
+  if (left && !some) return declined(jobs);
+  return 1;
+}
+
 // The BWT decoders, device/bwt_decode_kernel.h (4-byte nodes, blocks below 16 MiB) and device/bwt_decode_wide_kernel.h (8-byte
 // nodes, the program at args[0] 5 .. 11), for a batch of host streams.  The host admits the streams (the rule, the range), so
 // every size is known and the room is checked before anything runs; then one upload, the kernels, a word per stream back, and the

@@ -237,6 +237,41 @@ struct UnlzResult { uint32_t out_len, ntok, status; };
 
 enum { kUnlzOk = 0, kUnlzBefore = 1, kUnlzEmpty = 2, kUnlzLong = 3, kUnlzFull = 4, kUnlzField = 5 };
 
+// ... streams long enough to be parsed in pieces (device/lz77_decode_wide_kernel.h).  A stream of npieces pieces of `piece` bytes
+// owns npieces * piece slots from tok_off on in each of three arrays: the pieces' provisional tokens (piece k's from slot
+// k * piece), the start states of their codes (4 bytes each, the same slots) and the stream's final list (from slot 0).
+static const uint32_t kUnlzWidePiece = 16u << 10;      // bytes of stream per piece
+static const uint32_t kUnlzWideRounds = 32;            // jump rounds before the batch is declined
+static inline uint32_t unlz_wide_piece_clamped(uint64_t bytes) {      // ZPAQ_AMD_UNLZ_WIDE_PIECE as the engine takes it: [64, 2^20], a multiple of 64
+  if (bytes < 64u) bytes = 64u;
+  if (bytes > (1u << 20)) bytes = 1u << 20;
+  return (uint32_t)((bytes + 63u) & ~63ull);
+}
+struct UnlzWideStream {
+  uint64_t in_off;       // first byte of the stream in the batch's buffer, a multiple of 4
+  uint64_t tok_off;      // first slot
+  uint32_t in_len;       // bytes
+  uint32_t piece0;       // the stream's first piece in the batch's piece tables
+  uint32_t npieces;      // (in_len + piece - 1) / piece
+  uint32_t level, rb, min_match, mbits;      // as in UnlzStream
+  uint32_t pad_;
+};
+struct UnlzWideRef { uint32_t stream, index; };       // piece g of the batch is piece `index` of stream `stream`
+// what the parse of a piece leaves: its list holds `codes` tokens that emit out_len bytes; end 0: it walked out of the piece and
+// {exit_pos, exit_t} is the state at the first code start at or behind the piece's end; 1: the stream ended there, as the program
+// ends it; 2: the list ends at a code the parser refuses (`status`) -- a verdict only if the true walk gets there
+struct UnlzWidePieceOut { uint32_t codes, out_len, exit_pos, exit_t, end, status; };
+// what the stitch leaves per piece: tokens first .. first + count of its list are the stream's tokens tok_base .. , and out_base is
+// what their positions lack (modulo 2^32)
+struct UnlzWideAdopt { uint32_t first, count, tok_base, out_base; };
+// ... and per stream: its UnlzResult; err = all ones, or (the first token that fails a check against its absolute position) << 3 |
+// the status it declines the stream with, which goes before r.status; the stream's pieces, and how many of them were adopted at
+// the state the walk entered them in, met after a serial stretch, walked serially to their end (the rest: a code leapt over them)
+struct UnlzWideStats { uint32_t pieces, entered, met, walked; };
+struct UnlzWideOut { UnlzResult r; uint32_t pad_; unsigned long long err; UnlzWideStats stats; };
+// where a decoded stream's output lies in the batch's (out_len >= 1, ntok tokens in its final list)
+struct UnlzWidePlace { uint64_t out_off; uint32_t out_len, ntok, stream, pad_; };
+
 // BWT streams back into their blocks (device/bwt_decode_kernel.h).  A stream is S[0 .. n] and idx in 4 bytes, low byte first.
 enum { kBwtTile = 4096, kBwtChunk = 64, kBwtStride = 256 };      // bytes per tile of the counting sort, per step of it, nodes per splitter
 struct BwtStream {

@@ -71,6 +71,18 @@ hipError_t launch_lz77_emit(const uint8_t* in_all, const LzBlock* blocks, uint32
 hipError_t launch_unlz_parse(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, void* toks, UnlzResult* res, hipStream_t st);
 hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, uint32_t nstreams, const void* toks, const UnlzResult* res,
                             const uint64_t* out_off, uint8_t* out_all, hipStream_t st);
+// ... streams parsed in pieces (device/lz77_decode_wide_kernel.h; the arrays as layout.h UnlzWideStream places them: prov, states
+// and fin hold a slot per stream byte rounded up to whole pieces).  launch_unlz_wide_parse leaves the final 16-byte tokens in fin
+// and outs[b] (layout.h UnlzWideOut: where err is not all ones its low three bits are the stream's status).  The caller places the outputs of the decoded, non-empty streams back to back (place, in
+// the order of the outputs; at most 2^31 bytes) and calls launch_unlz_wide_link, launch_unlz_wide_jump with a zeroed flag word per
+// round until a round leaves its flag zero (kUnlzWideRounds at the most), and launch_unlz_wide_emit.
+hipError_t launch_unlz_wide_parse(uint32_t level, const uint8_t* in_all, const UnlzWideStream* streams, uint32_t nstreams, const UnlzWideRef* refs, uint32_t npieces,
+                                  uint32_t piece, void* prov, uint32_t* states, UnlzWidePieceOut* pieces, void* fin, UnlzWideAdopt* adopt, UnlzWideOut* outs,
+                                  hipStream_t st);
+hipError_t launch_unlz_wide_link(const uint8_t* in_all, const UnlzWideStream* streams, const UnlzWidePlace* place, uint32_t nlive, uint32_t total,
+                                 const void* fin, uint32_t* w, hipStream_t st);
+hipError_t launch_unlz_wide_jump(uint32_t* w, uint32_t total, uint32_t* flag, hipStream_t st);
+hipError_t launch_unlz_wide_emit(const uint32_t* w, uint32_t total, uint8_t* out, hipStream_t st);
 // BWT streams back into their blocks (device/bwt_decode_kernel.h): count, scan, link, rank, offsets and emit for nstreams
 // admitted streams (layout.h bwt_stream_admitted) placed as `streams` says -- ntiles tiles of 256 words in hist, a word per node
 // in link, nsplit entries of 16 bytes in splitters.  status[b] = 0: out_all + out_off holds stream b's n bytes; 1: its path has

@@ -28,6 +28,7 @@
 #include "fragment_kernel.h"
 #include "lz77_codes_kernel.h"
 #include "lz77_decode_kernel.h"
+#include "lz77_decode_wide_kernel.h"
 #include "lz77_hash_kernel.h"
 #include "lz77_kernel.h"
 #include "lz77_wide_kernel.h"
@@ -131,6 +132,29 @@ __global__ __launch_bounds__(64) void unlz_copy_kernel(const uint8_t* in_all, co
                                                        const uint64_t* out_off, uint8_t* out_all) {
   unlz_copy_body(in_all, streams, toks, res, out_off, out_all);
 }
+
+// device/lz77_decode_wide_kernel.h: a stream parsed in pieces, copied by pointer jumping
+template <bool kBits>
+__global__ __launch_bounds__(64) void unlzw_piece_kernel(const uint8_t* in_all, const UnlzWideStream* streams, const UnlzWideRef* refs, uint32_t piece,
+                                                         uint4* prov, uint32_t* states, UnlzWidePieceOut* pieces) {
+  unlzw_piece_body<kBits>(in_all, streams, refs, piece, prov, states, pieces);
+}
+template <bool kBits>
+__global__ __launch_bounds__(64) void unlzw_stitch_kernel(const uint8_t* in_all, const UnlzWideStream* streams, uint32_t piece, const uint4* prov,
+                                                          const uint32_t* states, const UnlzWidePieceOut* pieces, uint4* fin, UnlzWideAdopt* adopt,
+                                                          UnlzWideOut* outs) {
+  unlzw_stitch_body<kBits>(in_all, streams, piece, prov, states, pieces, fin, adopt, outs);
+}
+__global__ __launch_bounds__(256) void unlzw_finalize_kernel(const UnlzWideStream* streams, const UnlzWideRef* refs, uint32_t piece, const uint4* prov,
+                                                             const UnlzWideAdopt* adopt, uint4* fin, UnlzWideOut* outs) {
+  unlzw_finalize_body(streams, refs, piece, prov, adopt, fin, outs);
+}
+__global__ __launch_bounds__(256) void unlzw_link_kernel(const uint8_t* in_all, const UnlzWideStream* streams, const UnlzWidePlace* place, uint32_t nlive,
+                                                         uint32_t total, const uint4* fin, uint32_t* w) {
+  unlzw_link_body(in_all, streams, place, nlive, total, fin, w);
+}
+__global__ __launch_bounds__(256) void unlzw_jump_kernel(uint32_t* w, uint32_t total, uint32_t* flag) { unlzw_jump_body(w, total, flag); }
+__global__ __launch_bounds__(256) void unlzw_emit_kernel(const uint32_t* w, uint32_t total, uint8_t* out) { unlzw_emit_body(w, total, out); }
 
 __global__ __launch_bounds__(64) void unbwt_count_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t* hist) {
   unbwt_count_body(in_all, streams, nstreams, hist);
@@ -437,6 +461,52 @@ hipError_t launch_unlz_copy(const uint8_t* in_all, const UnlzStream* streams, ui
   if (!nstreams) return hipSuccess;
   if (nstreams > 65535u) return hipErrorInvalidValue;
   hipLaunchKernelGGL(unlz_copy_kernel, dim3(nstreams), dim3(64), 0, st, in_all, streams, (const uint4*)toks, res, out_off, out_all);
+  return hipGetLastError();
+}
+
+// device/lz77_decode_wide_kernel.h, the first half: the pieces' lists, the stitch (over `adopt`, zeroed here), the final lists.
+// Leaves outs[b] = {{out_len, ntok, status}, the first failing token's key (all ones: none), the counts}.
+// level: the batch's (1 or 2; a stream of the other is declined).
+hipError_t launch_unlz_wide_parse(uint32_t level, const uint8_t* in_all, const UnlzWideStream* streams, uint32_t nstreams, const UnlzWideRef* refs, uint32_t npieces,
+                                  uint32_t piece, void* prov, uint32_t* states, UnlzWidePieceOut* pieces, void* fin, UnlzWideAdopt* adopt, UnlzWideOut* outs,
+                                  hipStream_t st) {
+  if (!nstreams) return hipSuccess;
+  const uint64_t fblocks = (uint64_t)npieces * ((piece + 255u) / 256u);
+  if (fblocks >= (1ull << 31)) return hipErrorInvalidValue;
+  if (npieces) {
+    hipError_t rc = hipMemsetAsync(adopt, 0, sizeof(UnlzWideAdopt) * (size_t)npieces, st);
+    if (rc != hipSuccess) return rc;
+    if (level == 1u) hipLaunchKernelGGL(unlzw_piece_kernel<true>, dim3(npieces), dim3(64), 0, st, in_all, streams, refs, piece, (uint4*)prov, states, pieces);
+    else hipLaunchKernelGGL(unlzw_piece_kernel<false>, dim3(npieces), dim3(64), 0, st, in_all, streams, refs, piece, (uint4*)prov, states, pieces);
+  }
+  if (level == 1u)
+    hipLaunchKernelGGL(unlzw_stitch_kernel<true>, dim3(nstreams), dim3(64), 0, st, in_all, streams, piece, (const uint4*)prov, (const uint32_t*)states,
+                       (const UnlzWidePieceOut*)pieces, (uint4*)fin, adopt, outs);
+  else
+    hipLaunchKernelGGL(unlzw_stitch_kernel<false>, dim3(nstreams), dim3(64), 0, st, in_all, streams, piece, (const uint4*)prov, (const uint32_t*)states,
+                       (const UnlzWidePieceOut*)pieces, (uint4*)fin, adopt, outs);
+  if (npieces)
+    hipLaunchKernelGGL(unlzw_finalize_kernel, dim3((unsigned)fblocks), dim3(256), 0, st, streams, refs, piece, (const uint4*)prov,
+                       (const UnlzWideAdopt*)adopt, (uint4*)fin, outs);
+  return hipGetLastError();
+}
+// ... the second half: every output byte's word, from the final lists of the `nlive` decoded streams (`total` bytes in all)
+hipError_t launch_unlz_wide_link(const uint8_t* in_all, const UnlzWideStream* streams, const UnlzWidePlace* place, uint32_t nlive, uint32_t total,
+                                 const void* fin, uint32_t* w, hipStream_t st) {
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(unlzw_link_kernel, dim3(grid_for(total)), dim3(256), 0, st, in_all, streams, place, nlive, total, (const uint4*)fin, w);
+  return hipGetLastError();
+}
+// ... one jump round; *flag (zero before) becomes 1 if another is needed
+hipError_t launch_unlz_wide_jump(uint32_t* w, uint32_t total, uint32_t* flag, hipStream_t st) {
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(unlzw_jump_kernel, dim3(grid_for(total)), dim3(256), 0, st, w, total, flag);
+  return hipGetLastError();
+}
+// ... and the bytes
+hipError_t launch_unlz_wide_emit(const uint32_t* w, uint32_t total, uint8_t* out, hipStream_t st) {
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(unlzw_emit_kernel, dim3(grid_for(total)), dim3(256), 0, st, w, total, out);
   return hipGetLastError();
 }
 

@@ -570,7 +570,7 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
 }
 
 namespace {
-std::atomic<U32> g_last_unlz_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0}, g_last_pcomp_segments{0};
+std::atomic<U32> g_last_unlz_segments{0}, g_last_unlz_wide_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0}, g_last_pcomp_segments{0};
 
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
@@ -656,12 +656,14 @@ bool une8_program(const std::vector<U8>& key, StreamProgram& u) {
 }  // namespace
 
 U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_order_relaxed); }
+U32 last_device_unlz_wide_segments() { return g_last_unlz_wide_segments.load(std::memory_order_relaxed); }
 U32 last_device_unbwt_segments() { return g_last_unbwt_segments.load(std::memory_order_relaxed); }
 U32 last_device_une8_segments() { return g_last_une8_segments.load(std::memory_order_relaxed); }
 U32 last_device_pcomp_segments() { return g_last_pcomp_segments.load(std::memory_order_relaxed); }
 
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
   g_last_unlz_segments.store(0, std::memory_order_relaxed);
+  g_last_unlz_wide_segments.store(0, std::memory_order_relaxed);
   g_last_unbwt_segments.store(0, std::memory_order_relaxed);
   g_last_une8_segments.store(0, std::memory_order_relaxed);
   g_last_pcomp_segments.store(0, std::memory_order_relaxed);
@@ -821,6 +823,45 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
       }
       counter.store(taken, std::memory_order_relaxed);
     };
+    // Long streams of the LZ77 inverses without E8E9 first (device/lz77_decode_wide_kernel.h: a stream parsed in pieces, copied by
+    // pointer jumping): inside a group whose program unlz_program recognises, the segments whose stream has at least
+    // ZPAQ_AMD_UNLZ_WIDE_FROM bytes (1 MiB; read per call: tests).  ZPAQ_AMD_DEVICE_UNLZ_WIDE=0|1 forces the route off or on for
+    // them, unset follows lz_unlz_wide_pays.  What it takes leaves the group; the rest goes on exactly as without it.
+    if (const int how = mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ_WIDE")) {
+      U64 wide_from = 1u << 20;
+      if (const char* v = getenv("ZPAQ_AMD_UNLZ_WIDE_FROM")) { const long long x = atoll(v); if (x > 0) wide_from = (U64)x; }
+      U32 taken = 0;
+      for (auto& kv : by_prog) {
+        if (!nprog || engine_device_count() <= 0) break;
+        const std::vector<U8>& key = kv.first;
+        const size_t skip = 3 + (key.size() - 2);
+        U64 bytes = 0;
+        std::vector<StreamJob> uj;
+        std::vector<size_t> cand;                             // (positions in kv.second)
+        for (size_t k = 0; k < kv.second.size(); ++k) {
+          const Seg& s = *segs[kv.second[k]];
+          if (s.decoded.size() - skip < wide_from) continue;
+          uj.push_back(StreamJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[kv.second[k]]});
+          cand.push_back(k);
+          bytes += s.decoded.size() - skip;
+        }
+        if (uj.empty() || (how != 1 && !lz_unlz_wide_pays(uj.size(), bytes))) continue;
+        StreamProgram u;
+        if (!unlz_program(key, u)) continue;                  // (last: it generates the programs it compares with)
+        std::string note;
+        if (engine_lz77_decode_wide((U32)u.kind, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
+        std::vector<char> gone(kv.second.size(), 0);
+        for (size_t c = 0; c < uj.size(); ++c) {
+          const size_t i = kv.second[cand[c]];
+          if (uj[c].status == 0) { on_device[i] = 1; gone[cand[c]] = 1; ++taken; }
+          else done[i].clear();
+        }
+        std::vector<size_t> left;
+        for (size_t k = 0; k < kv.second.size(); ++k) if (!gone[k]) left.push_back(kv.second[k]);
+        kv.second.swap(left);
+      }
+      g_last_unlz_wide_segments.store(taken, std::memory_order_relaxed);
+    }
     // The LZ77 inverses without E8E9 (device/lz77_decode_kernel.h: a wavefront per segment, not a lane): ZPAQ_AMD_DEVICE_UNLZ=0|1
     // forces the route off or on, unset follows lz_unlz_pays.
     route(mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ"), unlz_program, [](const StreamProgram&, U64 segs, U64 bytes) { return lz_unlz_pays(segs, bytes); },

@@ -66,6 +66,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
 U32 last_wide_sort_blocks();          // sorting blocks of this process's last compress_blocks call that the wide sorter sorted
 U32 last_wide_parse_blocks();         // ... and of those, the LZ77 blocks that were parsed on the device as well
 U32 last_device_unlz_segments();
+U32 last_device_unlz_wide_segments();   // ... that device/lz77_decode_wide_kernel.h decoded
 // ... that device/bwt_decode_kernel.h decoded
 U32 last_device_unbwt_segments();
 // ... that went through their stage's decoder and device/e8e9_kernel.h (the E8E9 methods)
