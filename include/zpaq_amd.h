@@ -476,6 +476,27 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
  * exists yet.  Any set value of ZPAQ_AMD_PCOMP keeps its meaning and the counter at 0.  ZPAQ_AMD_DEVICE_UNLZ and
  * ZPAQ_AMD_DEVICE_UNBWT never touch these segments.  The bytes are the same either way. */
 uint32_t zpq_last_device_une8_segments(void);
+/* Streams of the E8E9 forms of the LZ77 methods -- args[1] = 5 or 6 at any args[0] 0 .. 11 -- through the decoder for LONG
+ * streams (zpq_lz77_decode_device_wide: pieces, stitch, pointer jumping) and then the inverse filter, both on the device (DESIGN
+ * 4.5.10): the copy's bytes are emitted into rooms placed for device/e8e9_kernel.h, each on a multiple of 16 bytes, and filtered
+ * there before they go down.  The argument list and the statuses are zpq_e8e9_decode_device's and so is the contract per stream:
+ * status 0 -- out[b] holds, byte for byte, what zpq_postprocess_block makes of stream b; 1 declined, out[b] untouched -- whatever
+ * the wide LZ77 decoder declines, an output beyond 2^(args[0] + 20) bytes, or a chain a lane gave up.  A stream of any length
+ * is taken.  Range and sub-batches as for zpq_lz77_decode_device_wide, with the rooms' padding, 8 bytes per 4 KiB of output and 4
+ * bytes per e8 / e9 candidate and chain besides; the 2 GiB per batch are of the rooms.  ZPQ_E_OVERFLOW with every size reported
+ * and nothing written when a decoded block does not fit its buffer; ZPQ_E_UNSUPPORTED with a note without a device, for another
+ * kind of method, or outside the range.  zpq_last_unlz_wide_pieces and zpq_last_unlz_wide_rounds report this decoder's last call
+ * as they do for zpq_lz77_decode_device_wide; ZPAQ_AMD_UNLZ_WIDE_PIECE sets the piece here too. */
+int zpq_e8e9_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
+                                uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status);
+/* Segments of this process's last zpq_decompress call that went that way.  Inside a group that qualifies for
+ * zpq_last_device_une8_segments' route with an x.,5 or x.,6 program, the segments whose stream has at least
+ * ZPAQ_AMD_UNLZ_WIDE_FROM bytes (default 1 MiB; read per call) are candidates.  The route runs only when ZPAQ_AMD_DEVICE_UNE8 and
+ * ZPAQ_AMD_DEVICE_UNLZ_WIDE are both 1; either at 0, or any set value of ZPAQ_AMD_PCOMP, keeps it off, and with one or both unset
+ * it is off as well (e8_unlz_wide_pays; DESIGN 4.5.10 has the table and the rule).  What it decodes is counted here and in
+ * neither zpq_last_device_une8_segments nor zpq_last_device_unlz_wide_segments; what it declines, and the rest of the group, goes
+ * on exactly as without it, ZPAQ_AMD_DEVICE_UNE8's own route included.  The bytes are the same either way. */
+uint32_t zpq_last_device_une8_wide_segments(void);
 /* The generic route on its own: the PCOMP program `code` (the bytes without the two length bytes, ph and pm as in the block
  * header) over n raw streams on the device, one lane per stream (device/pcomp_kernel.h: the program is translated to HIP and
  * compiled at run time unless a code object for it is cached).  hint[b] = the expected size of output b or 0 (a segment's size

@@ -105,6 +105,9 @@ def lib():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_last_device_une8_segments.restype = C.c_uint32
     L.zpq_last_device_une8_segments.argtypes = []
+    L.zpq_e8e9_decode_device_wide.argtypes = L.zpq_e8e9_decode_device.argtypes
+    L.zpq_last_device_une8_wide_segments.restype = C.c_uint32
+    L.zpq_last_device_une8_wide_segments.argtypes = []
     L.zpq_pcomp_device.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
                                    C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_pcomp_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, _u8p, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -511,9 +514,10 @@ def last_device_unbwt_segments() -> int:
     return int(lib().zpq_last_device_unbwt_segments())
 
 
-def e8e9_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
+def e8e9_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0, wide: bool = False):
     """zpq_e8e9_decode_device: a batch of streams of an E8E9 method (args[1] 4 .. 7, the BWT at args[0] <= 4) back into their blocks
-    on the device.  caps = the output capacities; `guard` bytes of `fill` lie behind each.  Returns (return code, buffers -- cap +
+    on the device (wide: zpq_e8e9_decode_device_wide, args[1] 5 / 6 through the decoder that parses a stream in pieces).
+    caps = the output capacities; `guard` bytes of `fill` lie behind each.  Returns (return code, buffers -- cap +
     guard bytes each, as the call left them --, sizes, statuses: 0 decoded, 1 declined)."""
     n = len(streams)
     ins = [_arr(x) if len(x) else np.zeros(1, np.uint8) for x in streams]
@@ -525,8 +529,21 @@ def e8e9_decode_device(xmethod: str, streams: Sequence, caps: Sequence[int], gua
     OC = (C.c_size_t * n)(*caps)
     OL = (C.c_size_t * n)()
     ST = (C.c_int32 * n)()
-    rc = lib().zpq_e8e9_decode_device(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
+    entry = lib().zpq_e8e9_decode_device_wide if wide else lib().zpq_e8e9_decode_device
+    rc = entry(xmethod.encode(), IA, IL, n, OA, OC, OL, ST)
     return rc, [outs[i][:caps[i] + guard].tobytes() for i in range(n)], [int(x) for x in OL], [int(x) for x in ST]
+
+
+def e8e9_decode_device_wide(xmethod: str, streams: Sequence, caps: Sequence[int], guard: int = 0, fill: int = 0):
+    """zpq_e8e9_decode_device_wide: e8e9_decode_device for x.,5 / x.,6 through the decoder for long streams, the inverse filter
+    behind it (ZPAQ_AMD_UNLZ_WIDE_PIECE sets the piece; last_unlz_wide_pieces / last_unlz_wide_rounds report the call)."""
+    return e8e9_decode_device(xmethod, streams, caps, guard, fill, wide=True)
+
+
+def last_device_une8_wide_segments() -> int:
+    """Segments of the last decompress call that went through the decoder for long LZ77 streams and then the inverse E8E9 filter
+    (ZPAQ_AMD_DEVICE_UNE8 and ZPAQ_AMD_DEVICE_UNLZ_WIDE both 1)."""
+    return int(lib().zpq_last_device_une8_wide_segments())
 
 
 def last_device_une8_segments() -> int:

@@ -815,6 +815,21 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }
 
+// ... streams of x.,5 / x.,6 parsed in pieces, then filtered (device/lz77_decode_wide_kernel.h, device/e8e9_kernel.h)
+int zpq_e8e9_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
+                                size_t* outlen, int32_t* status) {
+  return decode_streams_device(xmethod, stream, len, n, out, cap, outlen, status,
+      [](const char* xm, const int* args) -> const char* {
+        return xm[0] == '0' || (args[1] != 5 && args[1] != 6) || args[0] < 0 || args[0] > 11 ? "not an LZ77 method behind E8E9 (args[1] 5 or 6, args[0] 0 .. 11)"
+                                                                                             : nullptr;
+      },
+      [](const int* args, std::vector<StreamJob>& jobs, std::string& note) {
+        return engine_e8e9_decode_wide(args[1], lz_offset_rb(args), (U32)args[2], (U32)(args[0] + 20), jobs, note);
+      });
+}
+
+uint32_t zpq_last_device_une8_wide_segments(void) { return last_device_une8_wide_segments(); }
+
 // A raw PCOMP program over a batch of raw streams on the device (device/pcomp_kernel.h through engine_pcomp) ...
 int zpq_pcomp_device(const uint8_t* code, size_t codelen, int ph, int pm, const uint8_t* const* stream, const uint32_t* len, uint32_t n,
                      const uint64_t* hint, uint8_t* const* out, const size_t* cap, size_t* outlen, int32_t* status) {

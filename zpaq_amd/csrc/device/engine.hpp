@@ -226,6 +226,19 @@ int engine_e8e9_decode(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<S
 // lz_unlz_pays, fixed before the measurement: from the smallest measured group at which the route beat both other settings in
 // all three alternations, never below 64 segments, off while no measurement exists.  No measurement exists.
 inline bool e8_une8_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
+// Streams of the methods x.,5 and x.,6 (kind; anything else: -1 + note) through the decoder that parses a stream in pieces, then
+// the inverse filter: engine_lz77_decode_wide with level = kind - 4, its outputs emitted into rooms placed for
+// device/e8e9_kernel.h -- each on a multiple of 16 bytes, rounded up to one -- and filtered there before they go down.  The
+// contract per stream is engine_e8e9_decode's; 1 / 0 / -1, the sub-batches and ZPAQ_AMD_UNLZ_WIDE_PIECE as for
+// engine_lz77_decode_wide, whose counters (engine_last_unlz_wide_pieces, engine_last_unlz_wide_rounds) report this call too.  The
+// rooms' padding, the tiles' counts and the list of seeds and breaks count against the budget besides what that decoder holds;
+// the 2 GiB are of the rooms.  An empty output never enters the filter's list.
+int engine_e8e9_decode_wide(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note);
+// Whether the segments of an x.,5 / x.,6 group whose streams are long enough (host/blocks.cpp: ZPAQ_AMD_UNLZ_WIDE_FROM) take that
+// route unless ZPAQ_AMD_DEVICE_UNE8 and ZPAQ_AMD_DEVICE_UNLZ_WIDE both say 1.  The rule is the one of lz_unlz_wide_pays, fixed
+// before the measurement: from the smallest measured stream size at which the route beat both other settings in all three
+// alternations on every kind of data.  Off: no default rests on a measurement of this shape yet (DESIGN 4.5.10 has the table).
+inline bool e8_unlz_wide_pays(U64 /*segments*/, U64 /*stream_bytes*/) { return false; }
 // The archiver's content-defined fragments of a batch of files on the device (device/fragment_kernel.h): the files
 // are uploaded and divided into pieces of kFragPiece bytes, or 64 smallest fragments where that is more (ZPAQ_AMD_FRAG_PIECE, in
 // bytes, read per call, overrides both: tests).

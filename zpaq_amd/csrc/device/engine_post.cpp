@@ -258,14 +258,23 @@ int engine_lz77_decode(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<
 // changes nothing, emitted; the outputs down.  kUnlzwRan: status and out_len of its jobs are final.  kUnlzwShort: some decoded
 // block does not fit its job's buffer -- every out_len is reported, nothing was written.  Otherwise nothing was delivered either
 // and `note` says why -- kUnlzwOver: the batch does not fit the budget or 2 GiB of output; kUnlzwBroken: a launch failed.
+// P.e8: the method's program filters M before it writes it out (x.,5 / x.,6).  Link and jump run over the packed outputs as ever;
+// the bytes are emitted into rooms placed for device/e8e9_kernel.h (io_out: the rooms, each on a multiple of kE8Lane and rounded up
+// to one; then w; then the filter's workspace), which runs over them before anything goes down.  An empty output is delivered as
+// empty and never enters the filter's list; a block a lane of the walk gave up is declined (status 1, out_len 0).
 namespace {
 enum { kUnlzwBroken = -1, kUnlzwOver = 0, kUnlzwRan = 1, kUnlzwShort = 2 };
-struct UnlzWideParams { U32 level, rb, min_match, mbits, piece; };
+struct UnlzWideParams { U32 level, rb, min_match, mbits, piece; bool e8; };
 std::atomic<U32> g_last_unlz_wide_pieces[4], g_last_unlz_wide_rounds{0};
 
 // what a stream holds on the device before its size is known: the slots of three arrays and the stream
 uint64_t unlz_wide_slots(U32 in_len, U32 piece) { return ((uint64_t)in_len + piece - 1) / piece * piece; }
-uint64_t unlz_wide_need(U32 in_len, U32 piece) { return 36 * unlz_wide_slots(in_len, piece) + align_up(in_len, 4) + 256; }
+// (e8: the room's padding, the block's entry and status, the counts of its first tile -- the rest of the filter's workspace, 8 bytes per
+// 4 KiB of output, is known only with the sizes)
+uint64_t unlz_wide_e8_need() { return kE8Lane + sizeof(E8Block) + 4 + 8; }
+uint64_t unlz_wide_need(U32 in_len, U32 piece, bool e8) {
+  return 36 * unlz_wide_slots(in_len, piece) + align_up(in_len, 4) + 256 + (e8 ? unlz_wide_e8_need() : 0);
+}
 
 int unlz_wide_run(Engine& e, const UnlzWideParams& P, std::vector<StreamJob>& jobs, const size_t* who, size_t m, U32 counts[4], U32& rounds, std::string& note) {
   std::vector<UnlzWideStream> st(m);
@@ -299,9 +308,11 @@ int unlz_wide_run(Engine& e, const UnlzWideParams& P, std::vector<StreamJob>& jo
   const uint64_t o_st = cv.take(m * sizeof(UnlzWideStream));
   const uint64_t o_outs = cv.take(m * sizeof(UnlzWideOut));
   const uint64_t o_place = cv.take(m * sizeof(UnlzWidePlace));
+  const uint64_t o_dst = P.e8 ? cv.take(8 * m) : 0;
   const uint64_t o_flags = cv.take(4 * kUnlzWideRounds);
   const uint64_t ws = cv.at + 256;
-  if (ws + in_bytes + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return kUnlzwOver; }
+  const uint64_t f_least = P.e8 ? kE8Lane * (uint64_t)m + une8_ws(m, m).bytes : 0;      // were every output one tile
+  if (ws + in_bytes + f_least + (1u << 20) > e.budget) { note = "decoder workspace exceeds the device budget"; return kUnlzwOver; }
   e.io_in.ensure(in_bytes + 64);
   e.arena.ensure(ws);
   uint8_t* const ab = (uint8_t*)e.arena.p;
@@ -321,28 +332,34 @@ int unlz_wide_run(Engine& e, const UnlzWideParams& P, std::vector<StreamJob>& jo
   HIP_CHECK(hipStreamSynchronize(e.stream));
   std::vector<UnlzResult> res(m);
   std::vector<UnlzWidePlace> place;
-  std::vector<uint64_t> off(m);
-  uint64_t room = 0;
+  std::vector<uint64_t> off(m), dst;
+  uint64_t room = 0, placed = 0;                    // the outputs packed (w's index space); in their rooms (e8: aligned, else the same)
   bool fits = true;
+  E8List fl;                                        // e8: the decoded, non-empty blocks as the filter sees them
   for (size_t k = 0; k < m; ++k) {
     StreamJob& j = jobs[who[k]];
     const UnlzWideStats& c = outs[k].stats;
     res[k] = outs[k].r;
     if (outs[k].err != ~0ull) res[k].status = (uint32_t)(outs[k].err & 7u);        // the first token that failed a position check
     counts[0] += c.pieces; counts[1] += c.entered; counts[2] += c.met; counts[3] += c.walked;
-    off[k] = room;
+    off[k] = placed;
     if (res[k].status != kUnlzOk) continue;
     j.out_len = res[k].out_len;
-    if (res[k].out_len) place.push_back(UnlzWidePlace{room, res[k].out_len, res[k].ntok, (uint32_t)k, 0u});
+    if (res[k].out_len) {
+      place.push_back(UnlzWidePlace{room, res[k].out_len, res[k].ntok, (uint32_t)k, 0u});
+      if (P.e8) { dst.push_back(placed); fl.add(k, placed, res[k].out_len); }
+    }
     room += res[k].out_len;
+    placed += P.e8 ? e8_room(res[k].out_len) : res[k].out_len;
     if (!j.vec && res[k].out_len > j.cap) fits = false;
   }
-  if (room > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return kUnlzwOver; }
-  const uint64_t w_off = align_up(room, 256);
-  if (ws + in_bytes + w_off + 4 * room + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; return kUnlzwOver; }
+  if (placed > (1ull << 31)) { note = "more than 2 GiB of output in one batch"; return kUnlzwOver; }
+  const uint64_t w_off = align_up(placed, 256);
+  const uint64_t f_off = P.e8 ? align_up(w_off + 4 * room, 256) : w_off + 4 * room, f_ws = P.e8 ? fl.ws_bytes() : 0;
+  if (ws + in_bytes + f_off + f_ws + (1u << 20) > e.budget) { note = "the decoded blocks exceed the device budget"; return kUnlzwOver; }
   if (!fits) return kUnlzwShort;
   if (room) {
-    e.io_out.ensure(w_off + 4 * room + 64);
+    e.io_out.ensure(f_off + f_ws + 64);
     uint32_t* const w = (uint32_t*)((uint8_t*)e.io_out.p + w_off);
     uint32_t* const d_flags = (uint32_t*)(ab + o_flags);
     HIP_CHECK(hipMemcpyAsync(ab + o_place, place.data(), place.size() * sizeof(UnlzWidePlace), hipMemcpyHostToDevice, e.stream));
@@ -359,8 +376,18 @@ int unlz_wide_run(Engine& e, const UnlzWideParams& P, std::vector<StreamJob>& jo
       if (r + 1 > rounds) rounds = r + 1;
       if (!more) break;
     }
-    rc = launch_unlz_wide_emit(w, (uint32_t)room, (uint8_t*)e.io_out.p, e.stream);
+    if (P.e8) {
+      HIP_CHECK(hipMemcpyAsync(ab + o_dst, dst.data(), 8 * dst.size(), hipMemcpyHostToDevice, e.stream));
+      rc = launch_unlz_wide_emit_placed(w, (const UnlzWidePlace*)(ab + o_place), (const uint64_t*)(ab + o_dst), (uint32_t)place.size(), (uint32_t)room,
+                                        (uint8_t*)e.io_out.p, e.stream);
+    } else rc = launch_unlz_wide_emit(w, (uint32_t)room, (uint8_t*)e.io_out.p, e.stream);
     if (launch_failed(rc, "device LZ77 decoder failed: ", note)) return kUnlzwBroken;
+    if (P.e8) {                                     // (the streams in io_in are dead from here on: the filter's list goes there)
+      std::vector<char> lost;
+      // (a list beyond the budget is this batch's size, no failure of the device)
+      if (!fl.run(e, f_off, ws + f_off + f_ws, m, lost, note)) return note.find("budget") == std::string::npos ? kUnlzwBroken : kUnlzwOver;
+      for (size_t k = 0; k < m; ++k) if (lost[k]) { res[k].status = kUnlzLong; jobs[who[k]].out_len = 0; }
+    }
   }
   for (size_t k = 0; k < m; ++k) if (res[k].status == kUnlzOk) deliver(e, jobs[who[k]], off[k], res[k].out_len);
   HIP_CHECK(hipStreamSynchronize(e.stream));
@@ -377,7 +404,7 @@ U32 engine_last_unlz_wide_rounds() { return g_last_unlz_wide_rounds.load(std::me
 // stream by stream; only a stream that does not fit alone is declined (status 1; -1 + note when nothing else was decoded).  Jobs
 // with buffers of their own run as one batch or not at all: nothing may be written before every size is known.  After a failed
 // launch nothing more is started.
-int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+static int lz77_decode_wide_batch(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note, bool e8) {
   const size_t n = jobs.size();
   for (int k = 0; k < 4; ++k) g_last_unlz_wide_pieces[k].store(0, std::memory_order_relaxed);
   g_last_unlz_wide_rounds.store(0, std::memory_order_relaxed);
@@ -387,7 +414,7 @@ int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::ve
   if (n > 65535 || (level != 1 && level != 2) || rb > 7 || min_match > 255 || mbits > 32) { note = "batch outside the device decoder's range"; return -1; }
   U64 piece = kUnlzWidePiece;
   if (const char* v = getenv("ZPAQ_AMD_UNLZ_WIDE_PIECE")) { const long long x = atoll(v); if (x > 0) piece = (U64)x; }
-  const UnlzWideParams P{level, rb, min_match, mbits, unlz_wide_piece_clamped(piece)};
+  const UnlzWideParams P{level, rb, min_match, mbits, unlz_wide_piece_clamped(piece), e8};
   std::vector<size_t> who(n);
   for (size_t i = 0; i < n; ++i) who[i] = i;
   U32 counts[4] = {0, 0, 0, 0}, rounds = 0;
@@ -400,7 +427,7 @@ int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::ve
     if (all_vec) {
       uint64_t need = 0;
       for (end = from; end < n; ++end) {
-        need += unlz_wide_need(jobs[end].in_len, P.piece);
+        need += unlz_wide_need(jobs[end].in_len, P.piece, e8);
         if (end > from && need > e.budget / 2) break;
       }
     }
@@ -423,6 +450,17 @@ int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::ve
   g_last_unlz_wide_rounds.store(rounds, std::memory_order_relaxed);
   if (left && !some) return declined(jobs);
   return 1;
+}
+int engine_lz77_decode_wide(U32 level, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+  return lz77_decode_wide_batch(level, rb, min_match, mbits, jobs, note, false);
+}
+int engine_e8e9_decode_wide(int kind, U32 rb, U32 min_match, U32 mbits, std::vector<StreamJob>& jobs, std::string& note) {
+  if (kind != 5 && kind != 6) {
+    for (StreamJob& j : jobs) { j.status = 1; j.out_len = 0; }
+    note = "batch outside the device decoder's range";
+    return -1;
+  }
+  return lz77_decode_wide_batch((U32)(kind - 4), rb, min_match, mbits, jobs, note, true);
 }
 
 // The BWT decoders, device/bwt_decode_kernel.h (4-byte nodes, blocks below 16 MiB) and device/bwt_decode_wide_kernel.h (8-byte

@@ -28,6 +28,8 @@
 //                          interleaving of lanes reaches the same fixed point; no lane waits for another.  A round that leaves a
 //                          word unresolved raises the round's flag and the host launches the next (depth d: ceil(log2 d) rounds).
 //   unlzw_emit_kernel      out[p] = the byte w[p] holds.
+//   unlzw_emit_placed_kernel   the same bytes, each stream's at an offset of its own: the blocks as the inverse E8E9 filter takes
+//                          them (device/e8e9_kernel.h), which runs behind this stage for the methods x.,5 and x.,6.
 #pragma once
 #include "lz77_decode_kernel.h"
 
@@ -392,6 +394,18 @@ __device__ __forceinline__ void unlzw_jump_body(uint32_t* w, uint32_t total, uin
 __device__ __forceinline__ void unlzw_emit_body(const uint32_t* w, uint32_t total, uint8_t* out) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p < total) out[p] = (uint8_t)w[p];
+}
+
+// (6') ... for the inverse E8E9 filter behind this stage (device/e8e9_kernel.h): the words stay packed -- link and jump never see a
+// gap -- and the bytes go where the filter wants its blocks, stream place[a]'s at dst_off[a] (a multiple of kE8Lane, the room
+// behind it rounded up to one; the padding is not written).  A lane per packed byte q < total, the stream as unlzw_link_body finds it.
+__device__ __forceinline__ void unlzw_emit_placed_body(const uint32_t* w, const UnlzWidePlace* place, const uint64_t* dst_off, uint32_t nlive,
+                                                       uint32_t total, uint8_t* out) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= total) return;
+  uint32_t a = 0, z = nlive;                                    // the last stream whose output starts at or below q
+  while (z - a > 1u) { const uint32_t mid = a + ((z - a) >> 1); if (place[mid].out_off <= q) a = mid; else z = mid; }
+  out[dst_off[a] + (q - (uint32_t)place[a].out_off)] = (uint8_t)w[q];
 }
 
 }  // namespace zpq

@@ -83,6 +83,11 @@ hipError_t launch_unlz_wide_link(const uint8_t* in_all, const UnlzWideStream* st
                                  const void* fin, uint32_t* w, hipStream_t st);
 hipError_t launch_unlz_wide_jump(uint32_t* w, uint32_t total, uint32_t* flag, hipStream_t st);
 hipError_t launch_unlz_wide_emit(const uint32_t* w, uint32_t total, uint8_t* out, hipStream_t st);
+// ... or, in front of the inverse E8E9 filter, launch_unlz_wide_emit_placed: link and jump as above over the packed outputs, then
+// the bytes of stream place[a] at out + dst_off[a] (the caller's offsets, multiples of 16 with the rooms rounded up, as launch_une8_mark
+// takes its blocks; the padding is not written).
+hipError_t launch_unlz_wide_emit_placed(const uint32_t* w, const UnlzWidePlace* place, const uint64_t* dst_off, uint32_t nlive, uint32_t total, uint8_t* out,
+                                        hipStream_t st);
 // BWT streams back into their blocks (device/bwt_decode_kernel.h): count, scan, link, rank, offsets and emit for nstreams
 // admitted streams (layout.h bwt_stream_admitted) placed as `streams` says -- ntiles tiles of 256 words in hist, a word per node
 // in link, nsplit entries of 16 bytes in splitters.  status[b] = 0: out_all + out_off holds stream b's n bytes; 1: its path has

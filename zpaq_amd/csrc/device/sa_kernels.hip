@@ -155,6 +155,10 @@ __global__ __launch_bounds__(256) void unlzw_link_kernel(const uint8_t* in_all, 
 }
 __global__ __launch_bounds__(256) void unlzw_jump_kernel(uint32_t* w, uint32_t total, uint32_t* flag) { unlzw_jump_body(w, total, flag); }
 __global__ __launch_bounds__(256) void unlzw_emit_kernel(const uint32_t* w, uint32_t total, uint8_t* out) { unlzw_emit_body(w, total, out); }
+__global__ __launch_bounds__(256) void unlzw_emit_placed_kernel(const uint32_t* w, const UnlzWidePlace* place, const uint64_t* dst_off, uint32_t nlive,
+                                                                uint32_t total, uint8_t* out) {
+  unlzw_emit_placed_body(w, place, dst_off, nlive, total, out);
+}
 
 __global__ __launch_bounds__(64) void unbwt_count_kernel(const uint8_t* in_all, const BwtStream* streams, uint32_t nstreams, uint32_t* hist) {
   unbwt_count_body(in_all, streams, nstreams, hist);
@@ -507,6 +511,14 @@ hipError_t launch_unlz_wide_jump(uint32_t* w, uint32_t total, uint32_t* flag, hi
 hipError_t launch_unlz_wide_emit(const uint32_t* w, uint32_t total, uint8_t* out, hipStream_t st) {
   if (!total) return hipSuccess;
   hipLaunchKernelGGL(unlzw_emit_kernel, dim3(grid_for(total)), dim3(256), 0, st, w, total, out);
+  return hipGetLastError();
+}
+// ... or the bytes of stream place[a] at out + dst_off[a], for the filter behind the stage (the words stay packed)
+hipError_t launch_unlz_wide_emit_placed(const uint32_t* w, const UnlzWidePlace* place, const uint64_t* dst_off, uint32_t nlive, uint32_t total, uint8_t* out,
+                                        hipStream_t st) {
+  if (!total) return hipSuccess;
+  if (!nlive) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(unlzw_emit_placed_kernel, dim3(grid_for(total)), dim3(256), 0, st, w, place, dst_off, nlive, total, out);
   return hipGetLastError();
 }
 

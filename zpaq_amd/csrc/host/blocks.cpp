@@ -570,7 +570,8 @@ std::vector<std::vector<U8>> decode_payload_segments(const std::vector<U8>& head
 }
 
 namespace {
-std::atomic<U32> g_last_unlz_segments{0}, g_last_unlz_wide_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0}, g_last_pcomp_segments{0};
+std::atomic<U32> g_last_unlz_segments{0}, g_last_unlz_wide_segments{0}, g_last_unbwt_segments{0}, g_last_une8_segments{0}, g_last_une8_wide_segments{0},
+    g_last_pcomp_segments{0};
 
 // A PCOMP program (key: ph pm code) that is one of the LZ77 inverses without E8E9 make_config generates, recognised by
 // generating it again and comparing byte for byte (tools/gen_pcomp_std.cpp enumerates the standard programs the same way).
@@ -659,6 +660,7 @@ U32 last_device_unlz_segments() { return g_last_unlz_segments.load(std::memory_o
 U32 last_device_unlz_wide_segments() { return g_last_unlz_wide_segments.load(std::memory_order_relaxed); }
 U32 last_device_unbwt_segments() { return g_last_unbwt_segments.load(std::memory_order_relaxed); }
 U32 last_device_une8_segments() { return g_last_une8_segments.load(std::memory_order_relaxed); }
+U32 last_device_une8_wide_segments() { return g_last_une8_wide_segments.load(std::memory_order_relaxed); }
 U32 last_device_pcomp_segments() { return g_last_pcomp_segments.load(std::memory_order_relaxed); }
 
 void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, size_t)>& sink) {
@@ -666,6 +668,7 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
   g_last_unlz_wide_segments.store(0, std::memory_order_relaxed);
   g_last_unbwt_segments.store(0, std::memory_order_relaxed);
   g_last_une8_segments.store(0, std::memory_order_relaxed);
+  g_last_une8_wide_segments.store(0, std::memory_order_relaxed);
   g_last_pcomp_segments.store(0, std::memory_order_relaxed);
   struct Seg {
     FoundSegment fs;
@@ -875,6 +878,50 @@ void decode_archive(const U8* a, size_t n, const std::function<void(const U8*, s
           [](const StreamProgram& u, std::vector<StreamJob>& uj, std::string& note) {
             return u.wide ? engine_bwt_decode_wide(u.mbits, false, uj, note) : engine_bwt_decode(u.mbits, uj, note);
           }, g_last_unbwt_segments);
+    // Long streams of the E8E9 forms of the LZ77 methods (x.,5 / x.,6): the decoder for long streams, then the inverse filter over
+    // its outputs (engine_e8e9_decode_wide).  Inside a group whose program une8_program recognises with kind 5 or 6, the segments
+    // whose stream has at least ZPAQ_AMD_UNLZ_WIDE_FROM bytes.  On when ZPAQ_AMD_DEVICE_UNE8 and ZPAQ_AMD_DEVICE_UNLZ_WIDE both say
+    // 1, off when either says 0; with one or both unset e8_unlz_wide_pays decides.  What it takes leaves the group; the rest goes
+    // on exactly as without it, the route below included.
+    {
+      const int h8 = mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNE8"), hw = mode ? 0 : device_route_mode("ZPAQ_AMD_DEVICE_UNLZ_WIDE");
+      if (h8 && hw) {
+        const bool forced = h8 == 1 && hw == 1;
+        U64 wide_from = 1u << 20;
+        if (const char* v = getenv("ZPAQ_AMD_UNLZ_WIDE_FROM")) { const long long x = atoll(v); if (x > 0) wide_from = (U64)x; }
+        U32 taken = 0;
+        for (auto& kv : by_prog) {
+          if (!nprog || engine_device_count() <= 0) break;
+          const std::vector<U8>& key = kv.first;
+          const size_t skip = 3 + (key.size() - 2);
+          U64 bytes = 0;
+          std::vector<StreamJob> uj;
+          std::vector<size_t> cand;                           // (positions in kv.second)
+          for (size_t k = 0; k < kv.second.size(); ++k) {
+            const Seg& s = *segs[kv.second[k]];
+            if (s.decoded.size() - skip < wide_from) continue;
+            uj.push_back(StreamJob{s.decoded.data() + skip, (U32)(s.decoded.size() - skip), nullptr, 0, &done[kv.second[k]]});
+            cand.push_back(k);
+            bytes += s.decoded.size() - skip;
+          }
+          if (uj.empty() || (!forced && !e8_unlz_wide_pays(uj.size(), bytes))) continue;
+          StreamProgram u;
+          if (!une8_program(key, u) || (u.kind != 5 && u.kind != 6)) continue;      // (last: it generates the programs it compares with)
+          std::string note;
+          if (engine_e8e9_decode_wide(u.kind, u.rb, u.min_match, u.mbits, uj, note) != 1) continue;
+          std::vector<char> gone(kv.second.size(), 0);
+          for (size_t c = 0; c < uj.size(); ++c) {
+            const size_t i = kv.second[cand[c]];
+            if (uj[c].status == 0) { on_device[i] = 1; gone[cand[c]] = 1; ++taken; }
+            else done[i].clear();
+          }
+          std::vector<size_t> left;
+          for (size_t k = 0; k < kv.second.size(); ++k) if (!gone[k]) left.push_back(kv.second[k]);
+          kv.second.swap(left);
+        }
+        g_last_une8_wide_segments.store(taken, std::memory_order_relaxed);
+      }
+    }
     // The E8E9 methods likewise: their stage's decoder, then the inverse filter over its output on the device
     // (device/e8e9_kernel.h: the scan is serial only along short chains).  ZPAQ_AMD_DEVICE_UNE8=0|1 forces it off or on, unset
     // follows e8_une8_pays.
