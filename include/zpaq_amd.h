@@ -497,6 +497,25 @@ int zpq_e8e9_decode_device_wide(const char* xmethod, const uint8_t* const* strea
  * neither zpq_last_device_une8_segments nor zpq_last_device_unlz_wide_segments; what it declines, and the rest of the group, goes
  * on exactly as without it, ZPAQ_AMD_DEVICE_UNE8's own route included.  The bytes are the same either way. */
 uint32_t zpq_last_device_une8_wide_segments(void);
+/* The forward E8E9 filter (e8e9, libzpaq.cpp:6450-6459) of n buffers on the device, in place: the stage on its own.  The scan
+ * runs from the end of a buffer down and looks byte-serial; it is serial only along chains of e8 / e9 opcodes less than four
+ * bytes apart, and a lane walks each chain from its highest opcode whose original tail byte is 00 / ff
+ * (device/e8e9_forward_kernel.h).  max_steps: after that many serial steps a lane gives its buffer up (0: the engine's 2^20).
+ * status[b]: 0 -- data[b] holds, byte for byte, what zpq_e8e9 makes of it; 1 declined -- data[b] is untouched and the caller
+ * runs zpq_e8e9.  ZPQ_E_UNSUPPORTED with a note in zpq_last_error, and nothing touched, without a device or outside the range:
+ * 65 535 buffers and 2 GiB per batch; the buffers, 8 bytes per 4 KiB and 4 bytes per seed and per chain within the device
+ * budget. */
+int zpq_e8e9_device(uint8_t* const* data, const uint32_t* len, uint32_t n, uint32_t max_steps, int32_t* status);
+/* Blocks of this process's last zpq_compress_blocks call whose E8E9 filter (e8e9, libzpaq.cpp:6450-6459) ran on the device.  A
+ * block qualifies when its method has E8E9 in front of LZ77 or the BWT (x.,5 .. x.,7) and it takes one of the device routes of the
+ * pre-processing stage: the batched suffix sort with the parse behind it, the batched hash-table parse, or the wide sort of one
+ * block of 16 MiB and more.  The copy that was uploaded for that route is filtered there before the route reads it, and the
+ * filtered bytes come down into the caller's buffer, which holds what the reference leaves there whichever side filtered.
+ * ZPAQ_AMD_DEVICE_E8=0|1, read per call, forces that off or on for qualifying blocks; unset it is off: e8_forward_pays and
+ * e8_forward_wide_pays turn it on only from sizes at which it was measured to win on every kind of data.  A
+ * block whose walk exceeds the step cap (ZPAQ_AMD_E8_MAX_STEPS=<steps> lowers it: tests) is filtered by the host and not counted;
+ * x.,4 blocks and batches below the routes' thresholds are always filtered by the host.  The archives are the same either way. */
+uint32_t zpq_last_device_e8_blocks(void);
 /* The generic route on its own: the PCOMP program `code` (the bytes without the two length bytes, ph and pm as in the block
  * header) over n raw streams on the device, one lane per stream (device/pcomp_kernel.h: the program is translated to HIP and
  * compiled at run time unless a code object for it is cached).  hint[b] = the expected size of output b or 0 (a segment's size

@@ -105,6 +105,11 @@ def lib():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     L.zpq_last_device_une8_segments.restype = C.c_uint32
     L.zpq_last_device_une8_segments.argtypes = []
+    L.zpq_e8e9.argtypes = [_u8p, C.c_uint32]
+    L.zpq_e8e9.restype = None
+    L.zpq_e8e9_device.argtypes = [C.POINTER(_u8p), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
+    L.zpq_last_device_e8_blocks.argtypes = []
+    L.zpq_last_device_e8_blocks.restype = C.c_uint32
     L.zpq_e8e9_decode_device_wide.argtypes = L.zpq_e8e9_decode_device.argtypes
     L.zpq_last_device_une8_wide_segments.restype = C.c_uint32
     L.zpq_last_device_une8_wide_segments.argtypes = []
@@ -276,8 +281,10 @@ def decode_batch(plans: Sequence[Plan], payloads: Sequence, max_out: Sequence[in
 
 
 def compress_blocks(blocks: Sequence, method: str, filenames: Optional[Sequence[Optional[str]]] = None,
-                    comments: Optional[Sequence[Optional[str]]] = None, dosha1: bool = True) -> List[bytes]:
-    """Batched libzpaq::compressBlock: one ZPAQ block (archive bytes) per input buffer."""
+                    comments: Optional[Sequence[Optional[str]]] = None, dosha1: bool = True,
+                    inputs_after: Optional[list] = None) -> List[bytes]:
+    """Batched libzpaq::compressBlock: one ZPAQ block (archive bytes) per input buffer.  inputs_after: a list that receives the
+    input buffers as the call left them (E8E9 is applied in place, as the reference does)."""
     n = len(blocks)
     ins = [_arr(x).copy() for x in blocks]      # the call may modify inputs in place (E8E9)
     caps = [a.size + a.size // 4 + 8192 for a in ins]
@@ -305,6 +312,8 @@ def compress_blocks(blocks: Sequence, method: str, filenames: Optional[Sequence[
         rc = lib().zpq_compress_blocks(method.encode(), IA, IL, n, cstrs(filenames), cstrs(comments), int(dosha1),
                                        OA, OC, OL)
     _check(rc)
+    if inputs_after is not None:
+        inputs_after[:] = [a.tobytes() for a in ins]
     return [outs[i][:OL[i]].tobytes() for i in range(n)]
 
 
@@ -538,6 +547,39 @@ def e8e9_decode_device_wide(xmethod: str, streams: Sequence, caps: Sequence[int]
     """zpq_e8e9_decode_device_wide: e8e9_decode_device for x.,5 / x.,6 through the decoder for long streams, the inverse filter
     behind it (ZPAQ_AMD_UNLZ_WIDE_PIECE sets the piece; last_unlz_wide_pieces / last_unlz_wide_rounds report the call)."""
     return e8e9_decode_device(xmethod, streams, caps, guard, fill, wide=True)
+
+
+def e8e9(block) -> bytes:
+    """zpq_e8e9: the forward E8E9 filter of a block on the host (libzpaq.cpp:6450-6459)."""
+    a = _arr(block).copy() if len(block) else np.zeros(1, np.uint8)
+    lib().zpq_e8e9(_p(a), len(block))
+    return a[:len(block)].tobytes()
+
+
+def e8e9_device(blocks: Sequence, max_steps: int = 0, guard: int = 0, fill: int = 0):
+    """zpq_e8e9_device: the forward E8E9 filter of a batch of blocks on the device, in place.  The buffers lie in one arena with
+    `guard` bytes of `fill` behind each.  max_steps: the walk's cap on serial steps (0: the engine's).  Returns (return code,
+    buffers -- len + guard bytes each, as the call left them --, statuses: 0 filtered, 1 declined and untouched)."""
+    n = len(blocks)
+    offs, total = [], 0
+    for b in blocks:
+        offs.append(total)
+        total += len(b) + guard
+    arena = np.full(max(total, 1), fill, np.uint8)
+    for o, b in zip(offs, blocks):
+        if len(b):
+            arena[o:o + len(b)] = _arr(b)
+    base = arena.ctypes.data
+    DA = (_u8p * n)(*[C.cast(base + o, _u8p) for o in offs])
+    DL = (C.c_uint32 * n)(*[len(b) for b in blocks])
+    ST = (C.c_int32 * n)()
+    rc = lib().zpq_e8e9_device(DA, DL, n, int(max_steps), ST)
+    return rc, [arena[o:o + len(b) + guard].tobytes() for o, b in zip(offs, blocks)], [int(x) for x in ST]
+
+
+def last_device_e8_blocks() -> int:
+    """Blocks of the last compress_blocks call whose forward E8E9 filter ran on the device (ZPAQ_AMD_DEVICE_E8)."""
+    return int(lib().zpq_last_device_e8_blocks())
 
 
 def last_device_une8_wide_segments() -> int:

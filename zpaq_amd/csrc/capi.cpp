@@ -815,6 +815,22 @@ int zpq_e8e9_decode_device(const char* xmethod, const uint8_t* const* stream, co
 
 uint32_t zpq_last_device_une8_segments(void) { return last_device_une8_segments(); }
 
+// The forward filter on its own, n buffers in place (device/e8e9_forward_kernel.h)
+int zpq_e8e9_device(uint8_t* const* data, const uint32_t* len, uint32_t n, uint32_t max_steps, int32_t* status) {
+  ZPQ_TRY
+  if ((!data || !len || !status) && n) fail(ZPQ_E_ARG, "null argument");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!data[i] && len[i]) fail(ZPQ_E_ARG, "null argument");
+    status[i] = 1;
+  }
+  if (engine_device_count() <= 0) fail(ZPQ_E_UNSUPPORTED, "E8E9 filter on the device unavailable: no device");
+  std::string note;
+  if (!engine_e8e9_device(data, len, n, max_steps, status, note)) fail(ZPQ_E_UNSUPPORTED, "E8E9 filter on the device unavailable: " + note);
+  return ZPQ_OK;
+  ZPQ_CATCH
+}
+uint32_t zpq_last_device_e8_blocks(void) { return last_device_e8_blocks(); }
+
 // ... streams of x.,5 / x.,6 parsed in pieces, then filtered (device/lz77_decode_wide_kernel.h, device/e8e9_kernel.h)
 int zpq_e8e9_decode_device_wide(const char* xmethod, const uint8_t* const* stream, const uint32_t* len, uint32_t n, uint8_t* const* out, const size_t* cap,
                                 size_t* outlen, int32_t* status) {

@@ -77,7 +77,23 @@ bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, 
 // preprocess_block would make (n + 5 bytes).  false + note when the device declines (then the host does it all).
 // codes: LZBuffer's codes are written on the device as well (device/lz77_codes_kernel.h) -- a block of kind 1 / 2 then comes back
 // as its finished stream in SortOut::codes (coded = true) and its list of matches is not downloaded.
-struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0, rb = 0; };   // (min_match2, ht_bits: hash_job; rb: the coder)
+// e8 (null: the caller has filtered already, or the method has no E8E9): filter this block there.  `data` is then the unfiltered
+// block in a buffer the caller lets be written, and the stage runs device/e8e9_forward_kernel.h over the uploaded copy before
+// anything else reads it.  *e8 says what `data` holds, also when the stage returns false or throws: kE8Not the unfiltered bytes
+// still; kE8Device the filtered bytes, downloaded; kE8Host the filtered bytes, made by e8e9_forward here because the device
+// declined the block (a walk beyond the step cap, the list beyond the budget, a failed launch) and uploaded over the copy;
+// kE8InFlight a download that failed -- the buffer is in no known state and the caller must pass the error on.
+enum : U8 { kE8Not = 0, kE8Device = 1, kE8Host = 2, kE8InFlight = 3 };
+struct SortJob { const U8* data; U32 n; U32 kind, min_match, lookahead, bucket, checkbits; U32 min_match2 = 0, ht_bits = 0, rb = 0; U8* e8 = nullptr; };   // (min_match2, ht_bits: hash_job; rb: the coder)
+// The forward E8E9 filter on its own for n host buffers, in place (device/e8e9_forward_kernel.h): one upload, the filter, the
+// buffers with status 0 down again.  status[b] = 1: declined after max_steps serial steps (0: kE8MaxSteps), data[b] untouched.
+// false + note: outside the range (65 535 buffers, 2 GiB per batch, the device budget), nothing touched.
+bool engine_e8e9_device(U8* const* data, const U32* len, U32 n, U32 max_steps, int32_t* status, std::string& note);
+// Whether a batch of the suffix-sort or hash-parse route (blocks, bytes: its E8E9 blocks) / a wide block of n bytes is filtered on
+// the device when ZPAQ_AMD_DEVICE_E8 is unset.  The rule is that of sa_wide_pays: from the smallest measured size at which the
+// device filter won every alternation on every kind of data; false wherever nothing was measured.
+inline bool e8_forward_pays(U64 /*blocks*/, U64 /*bytes*/) { return false; }
+inline bool e8_forward_wide_pays(U64 /*n*/) { return false; }
 struct SortOut { std::vector<LzToken> toks; std::vector<U8> bwt; std::vector<U8> codes; bool coded = false; std::vector<U32> sa; bool parsed = false; };   // (sa, parsed: engine_sort_wide)
 // codes: 0 the lists come back; 1 the streams; 2 the streams when that pays -- decided per batch once the sizes are known, by
 // lz_codes_pay below (DESIGN 4.5.2 has the measurement behind it)

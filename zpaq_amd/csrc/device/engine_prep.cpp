@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdlib>
 
+#include "../host/common.hpp"
 #include "engine_internal.hpp"
 #include "fragment_stitch.hpp"
 #include "kernels.h"
@@ -66,6 +67,135 @@ static void upload_sa_inputs(Engine& e, const std::vector<HostItem>& items, uint
   s.staged = upload_staged(e, e.io_in.p, items, total, 0, in_bytes >= (1u << 20));
   HIP_CHECK(hipMemcpyAsync(meta, s.ptrs.data(), n * 8, hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemcpyAsync(meta + align_up(n * 8, 16), s.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, e.stream));
+}
+
+// ---- the forward E8E9 filter (device/e8e9_forward_kernel.h) ----
+
+// the walk's cap on serial steps: kE8MaxSteps, or less with ZPAQ_AMD_E8_MAX_STEPS=<steps>, read per call (tests: a decline
+// without a pathological megabyte)
+static uint32_t e8_max_steps() {
+  if (const char* v = getenv("ZPAQ_AMD_E8_MAX_STEPS")) { const long long x = atoll(v); if (x > 0 && x < (long long)kE8MaxSteps) return (uint32_t)x; }
+  return kE8MaxSteps;
+}
+
+// The filter's workspace, carved as the inverse's (engine_post.cpp une8_ws): the block table, the tiles' counts, the statuses,
+// the scan's scratch
+struct E8fWs { uint64_t o_cnt, o_st, o_tmp, bytes; size_t tmp_bytes; };
+static E8fWs e8f_ws(size_t m, uint64_t ntiles) {
+  E8fWs w;
+  Carve cv;
+  cv.take(m * sizeof(E8Block));
+  w.o_cnt = cv.take(4 * (2 * ntiles + 1));
+  w.o_st = cv.take(4 * m);
+  w.tmp_bytes = une8_scan_bytes((uint32_t)ntiles);
+  w.o_tmp = cv.take(w.tmp_bytes);
+  w.bytes = cv.at + 256;
+  return w;
+}
+
+// device/e8e9_forward_kernel.h over blocks that lie in d_buf, in place, wherever their offsets put them.  The caller has ensured
+// e8f_ws(..).bytes of io_out and has nothing live in io_out or in the arena buffer: the workspace goes to the front of the one,
+// the list of seeds and breaks -- sized from the two totals the host reads between the halves -- to the other.  held: what the
+// call holds besides the arena buffer; arena_else: what that buffer has to hold afterwards anyway.  status[k] = 0: block k is
+// filtered; 1: a lane gave it up, its bytes in d_buf are neither the input nor the output.  false + note: the device declines
+// them all (the list beyond the budget, a failed launch) -- treat d_buf's copies as for status 1.
+static bool engine_e8e9_forward(Engine& e, uint8_t* d_buf, const std::vector<E8Block>& blk, uint64_t ntiles, uint64_t held, uint64_t arena_else,
+                                uint32_t max_steps, std::vector<uint32_t>& status, std::string& note) {
+  const size_t m = blk.size();
+  status.assign(m, 1u);
+  if (!m) return true;
+  const E8fWs w = e8f_ws(m, ntiles);
+  uint8_t* const wb = (uint8_t*)e.io_out.p;
+  uint32_t* const cnt = (uint32_t*)(wb + w.o_cnt);
+  HIP_CHECK(hipMemcpyAsync(wb, blk.data(), m * sizeof(E8Block), hipMemcpyHostToDevice, e.stream));
+  hipError_t rc = launch_e8f_mark(d_buf, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)(wb + w.o_st), wb + w.o_tmp, w.tmp_bytes, e.stream);
+  if (launch_failed(rc, "device E8E9 filter failed: ", note)) return false;
+  uint32_t nseeds = 0, nlist = 0;
+  HIP_CHECK(hipMemcpyAsync(&nseeds, cnt + ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipMemcpyAsync(&nlist, cnt + 2 * ntiles, 4, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  if (nseeds) {
+    const uint64_t list_bytes = 4ull * nlist + 64;
+    if (held + std::max(arena_else, list_bytes) + (1u << 20) > e.budget) { note = "the filter's list exceeds the device budget"; return false; }
+    e.arena.ensure(list_bytes);
+    rc = launch_e8f_walk(d_buf, (const E8Block*)wb, (uint32_t)m, (uint32_t)ntiles, cnt, (uint32_t*)e.arena.p, nseeds, max_steps, (uint32_t*)(wb + w.o_st), e.stream);
+    if (launch_failed(rc, "device E8E9 filter failed: ", note)) return false;
+  }
+  HIP_CHECK(hipMemcpyAsync(status.data(), wb + w.o_st, 4 * m, hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  return true;
+}
+
+// The blocks of a batch that are to be filtered here (SortJob::e8): the list as the filter takes it, what it asks of io_out
+struct E8Batch {
+  std::vector<E8Block> blk;
+  std::vector<size_t> who;
+  uint64_t tiles = 0;
+  void add(size_t i, uint64_t off, uint32_t n) {
+    blk.push_back(E8Block{off, n, (uint32_t)tiles});
+    who.push_back(i);
+    tiles += e8_tiles(n);
+  }
+  uint64_t ws_bytes() const { return blk.empty() ? 0 : e8f_ws(blk.size(), tiles).bytes; }
+};
+static E8Batch e8_batch(const std::vector<SortJob>& jobs, const std::vector<HostItem>& items) {
+  E8Batch b;
+  for (size_t i = 0; i < jobs.size(); ++i) if (jobs[i].e8 && jobs[i].n) b.add(i, items[i].off, jobs[i].n);
+  return b;
+}
+// ... and the filter over them, once their bytes lie in io_in where `b` says and before anything else reads them.  A block the
+// device filtered comes down into the caller's buffer; one it declined is filtered there by the host and uploaded over the copy:
+// either way both sides hold e8e9_forward's bytes when this returns, and *SortJob::e8 says who made them.  A throw before any
+// download leaves every caller's buffer as it was (kE8Not) or filtered by the host (kE8Host).
+static void filter_uploaded(Engine& e, const std::vector<SortJob>& jobs, const E8Batch& b, uint64_t held, uint64_t arena_else) {
+  const size_t m = b.blk.size();
+  if (!m) return;
+  std::vector<uint32_t> st;
+  std::string why;
+  if (!engine_e8e9_forward(e, (uint8_t*)e.io_in.p, b.blk, b.tiles, held, arena_else, e8_max_steps(), st, why)) st.assign(m, 1u);
+  for (size_t k = 0; k < m; ++k) {
+    if (!st[k]) continue;
+    const SortJob& j = jobs[b.who[k]];
+    e8e9_forward(const_cast<U8*>(j.data), j.n);
+    *j.e8 = kE8Host;
+    HIP_CHECK(hipMemcpyAsync((uint8_t*)e.io_in.p + b.blk[k].off, j.data, j.n, hipMemcpyHostToDevice, e.stream));
+  }
+  for (size_t k = 0; k < m; ++k) {
+    if (st[k]) continue;
+    const SortJob& j = jobs[b.who[k]];
+    *j.e8 = kE8InFlight;
+    HIP_CHECK(hipMemcpyAsync(const_cast<U8*>(j.data), (const uint8_t*)e.io_in.p + b.blk[k].off, j.n, hipMemcpyDeviceToHost, e.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (size_t k = 0; k < m; ++k) if (!st[k]) *jobs[b.who[k]].e8 = kE8Device;
+}
+
+bool engine_e8e9_device(U8* const* data, const U32* len, U32 n, U32 max_steps, int32_t* status, std::string& note) {
+  for (U32 i = 0; i < n; ++i) status[i] = 1;
+  E8Batch b;
+  std::vector<HostItem> items(n);
+  uint64_t total = 0;
+  for (U32 i = 0; i < n; ++i) {
+    items[i] = HostItem{data[i], len[i], total};
+    b.add(i, total, len[i]);
+    total += len[i];
+  }
+  if (n > 65535 || total >= (1ull << 31)) { note = "batch outside the device filter's range"; return false; }
+  if (!n) return true;
+  EngineCall call;
+  Engine& e = call.e;
+  const uint64_t in_bytes = align_up(total, 256) + 64, ws = b.ws_bytes();
+  if (in_bytes + ws + (1u << 20) > e.budget) { note = "the batch exceeds the device budget"; return false; }
+  e.io_in.ensure(in_bytes);
+  e.io_out.ensure(ws);
+  const auto staged = upload_staged(e, e.io_in.p, items, total, 0, total >= (1u << 20));
+  std::vector<uint32_t> st;
+  if (!engine_e8e9_forward(e, (uint8_t*)e.io_in.p, b.blk, b.tiles, in_bytes + ws, 0, max_steps ? max_steps : kE8MaxSteps, st, note)) return false;
+  for (U32 i = 0; i < n; ++i)
+    if (!st[i] && len[i]) HIP_CHECK(hipMemcpyAsync(data[i], (const uint8_t*)e.io_in.p + b.blk[i].off, len[i], hipMemcpyDeviceToHost, e.stream));
+  HIP_CHECK(hipStreamSynchronize(e.stream));
+  for (U32 i = 0; i < n; ++i) status[i] = st[i] ? 1 : 0;
+  return true;
 }
 
 bool engine_suffix_arrays(const std::vector<std::pair<const U8*, U32>>& blocks, std::vector<std::vector<U32>>& sa, std::string& note) {
@@ -327,10 +457,14 @@ bool engine_sort_wide(const SortJob& job, SortOut& out, std::string& note, bool 
   if (parse && P.held(true) > e.budget) { parse = false; why = "sort + parse workspace exceeds the device budget"; }
   if (parse_or_nothing && !parse) { note = why.empty() ? "the block is not one the device parses" : why; return false; }   // (nothing was launched)
   if (P.held(false) > e.budget) { note = "suffix sort workspace exceeds the device budget"; return false; }
+  E8Batch e8;
+  if (job.e8) e8.add(0, 0, job.n);
+  const uint64_t out_bytes = std::max<uint64_t>(parse ? P.parse_out : P.sort_out, e8.ws_bytes());
   e.io_in.ensure(P.in_bytes + 64);
-  e.io_out.ensure(parse ? P.parse_out : P.sort_out);
+  e.io_out.ensure(out_bytes);
   e.arena.ensure(P.ws);
   HIP_CHECK(hipMemcpyAsync(e.io_in.p, job.data, n, hipMemcpyHostToDevice, e.stream));
+  filter_uploaded(e, std::vector<SortJob>(1, job), e8, P.in_bytes + out_bytes, P.ws);
   uint8_t* const ob = (uint8_t*)e.io_out.p;
   uint32_t rounds = 0;
   const uint32_t* d_rank = nullptr;
@@ -403,13 +537,15 @@ bool engine_sort_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   // ... and the coder's arrays (device/lz77_codes_kernel.h); the streams themselves take the place of the decisions, which are
   // dead behind the walk
   CodesLayout cl = codes_layout(cv, n, ntok + n);
-  const uint64_t out_bytes = (codes ? cl.end : cv.at) + 256;
+  const E8Batch e8 = e8_batch(jobs, items);
+  const uint64_t out_bytes = std::max<uint64_t>((codes ? cl.end : cv.at) + 256, e8.ws_bytes());
   if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "sort + parse workspace exceeds the device budget"; return false; }
   e.io_in.ensure(in_bytes + 64);
   e.io_out.ensure(out_bytes);
   e.arena.ensure(ws);
   SaInputs in;
   upload_sa_inputs(e, items, total, in_bytes, in);
+  filter_uploaded(e, jobs, e8, in_bytes + out_bytes, ws);
   uint8_t* const ob = (uint8_t*)e.io_out.p;
   HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 8 * n, e.stream));
@@ -472,12 +608,14 @@ bool engine_hash_preprocess(const std::vector<SortJob>& jobs, std::vector<SortOu
   const uint64_t o_blk = cv.take(n * sizeof(LzBlock));
   // ... and the coder's arrays; the streams take the place of the decisions (device/lz77_codes_kernel.h)
   CodesLayout cl = codes_layout(cv, n, ntok + n);
-  const uint64_t out_bytes = (codes ? cl.end : cv.at) + 256;
+  const E8Batch e8 = e8_batch(jobs, items);
+  const uint64_t out_bytes = std::max<uint64_t>((codes ? cl.end : cv.at) + 256, e8.ws_bytes());
   if (ws + in_bytes + out_bytes + (1u << 20) > e.budget) { note = "hash parse workspace exceeds the device budget"; return false; }
   e.io_in.ensure(in_bytes + 64);
   e.io_out.ensure(out_bytes);
   e.arena.ensure(ws);
   const auto staged = upload_staged(e, e.io_in.p, items, total, 0, in_bytes >= (1u << 20));
+  filter_uploaded(e, jobs, e8, in_bytes + out_bytes, ws);
   uint8_t* const ob = (uint8_t*)e.io_out.p;
   HIP_CHECK(hipMemcpyAsync(ob + o_blk, blk.data(), n * sizeof(LzBlock), hipMemcpyHostToDevice, e.stream));
   HIP_CHECK(hipMemsetAsync(ob + o_cnt, 0, 4 * n, e.stream));

@@ -112,6 +112,13 @@ hipError_t launch_une8_mark(const uint8_t* buf, const E8Block* blocks, uint32_t 
                             size_t tmp_bytes, hipStream_t st);
 hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
                             uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st);
+// The forward E8E9 filter over blocks in one device buffer, in place (device/e8e9_forward_kernel.h).  As the two above, except that
+// blocks[b].off is any byte offset and no room is rounded up: the blocks lie back to back as the sorters and parsers take them.
+// status[b] = 1: a lane gave block b up after max_steps steps, its bytes on the device are neither the input nor the output.
+hipError_t launch_e8f_mark(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt, uint32_t* status, void* tmp,
+                           size_t tmp_bytes, hipStream_t st);
+hipError_t launch_e8f_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
+                           uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st);
 // The archiver's content-defined fragments (device/fragment_kernel.h): a wavefront per job walks its file in `buf` from job.start
 // with a fresh state and appends a record per fragment to recs[job.rec_off ..], until the first cut at or beyond job.stop, a cut
 // whose end is in recs[job.merge_off .. + merge_cnt) (ascending ends), or the end of file; res[job] says how it ended.  The

@@ -24,6 +24,7 @@
 
 #include "bwt_decode_kernel.h"
 #include "bwt_decode_wide_kernel.h"
+#include "e8e9_forward_kernel.h"
 #include "e8e9_kernel.h"
 #include "fragment_kernel.h"
 #include "lz77_codes_kernel.h"
@@ -214,6 +215,18 @@ __global__ __launch_bounds__(256) void une8_scatter_kernel(const uint8_t* buf, c
 __global__ __launch_bounds__(256) void une8_walk_kernel(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan,
                                                         const uint32_t* list, uint32_t nseeds, uint32_t max_steps, uint32_t* status) {
   une8_walk_body(buf, blocks, nblocks, ntiles, scan, list, nseeds, max_steps, status);
+}
+__global__ __launch_bounds__(256) void e8f_mark_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt,
+                                                      uint32_t* status) {
+  e8f_mark_body(buf, blocks, nblocks, ntiles, cnt, status);
+}
+__global__ __launch_bounds__(256) void e8f_scatter_kernel(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles,
+                                                         const uint32_t* scan, uint32_t* list) {
+  e8f_scatter_body(buf, blocks, nblocks, ntiles, scan, list);
+}
+__global__ __launch_bounds__(256) void e8f_walk_kernel(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan,
+                                                      const uint32_t* list, uint32_t nseeds, uint32_t max_steps, uint32_t* status) {
+  e8f_walk_body(buf, blocks, nblocks, ntiles, scan, list, nseeds, max_steps, status);
 }
 
 __global__ __launch_bounds__(64) void frag_walk_kernel(const uint8_t* buf, const FragJob* jobs, uint32_t njobs, FragParams P, FragRec* recs,
@@ -586,6 +599,28 @@ hipError_t launch_une8_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblock
   if (nblocks > 65535u || ntiles < nblocks) return hipErrorInvalidValue;
   hipLaunchKernelGGL(une8_scatter_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t*)buf, blocks, nblocks, ntiles, scan, list);
   hipLaunchKernelGGL(une8_walk_kernel, dim3(grid_for(nseeds)), dim3(256), 0, st, buf, blocks, nblocks, ntiles, scan, (const uint32_t*)list, nseeds,
+                     max_steps, status);
+  return hipGetLastError();
+}
+
+// device/e8e9_forward_kernel.h, the two halves as the inverse's: the same arguments, the same checks, the same scratch
+hipError_t launch_e8f_mark(const uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, uint32_t* cnt, uint32_t* status, void* tmp,
+                           size_t tmp_bytes, hipStream_t st) {
+  if (!nblocks) return hipSuccess;
+  if (nblocks > 65535u || ntiles < nblocks || ntiles >= (1u << 30) || tmp_bytes < une8_scan_bytes(ntiles)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(e8f_mark_kernel, dim3(ntiles), dim3(256), 0, st, buf, blocks, nblocks, ntiles, cnt, status);
+  size_t need = tmp_bytes;
+  const hipError_t e = rocprim::exclusive_scan(tmp, need, cnt, cnt, 0u, (size_t)2 * ntiles + 1, rocprim::plus<uint32_t>(), st);
+  if (e != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+hipError_t launch_e8f_walk(uint8_t* buf, const E8Block* blocks, uint32_t nblocks, uint32_t ntiles, const uint32_t* scan, uint32_t* list,
+                           uint32_t nseeds, uint32_t max_steps, uint32_t* status, hipStream_t st) {
+  if (!nblocks || !nseeds) return hipSuccess;                   // (no seed: no hit, the breaks alone are not needed)
+  if (nblocks > 65535u || ntiles < nblocks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(e8f_scatter_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t*)buf, blocks, nblocks, ntiles, scan, list);
+  hipLaunchKernelGGL(e8f_walk_kernel, dim3(grid_for(nseeds)), dim3(256), 0, st, buf, blocks, nblocks, ntiles, scan, (const uint32_t*)list, nseeds,
                      max_steps, status);
   return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -207,6 +208,15 @@ int device_parse_wide_mode() {
 static const size_t kHashParseMinBlocks = 4;
 static const U64 kHashParseMinBytes = 1u << 20;
 
+// ZPAQ_AMD_DEVICE_E8=0|1, read per call: the forward E8E9 filter of blocks that take a device route runs on the host / there
+// (device/e8e9_forward_kernel.h); unset (2) follows e8_forward_pays and e8_forward_wide_pays (device/engine.hpp)
+static int device_e8_mode() {
+  const char* knob = getenv("ZPAQ_AMD_DEVICE_E8");
+  return !knob || !knob[0] ? 2 : (knob[0] != '0' ? 1 : 0);
+}
+static std::atomic<U32> g_last_device_e8_blocks{0};
+U32 last_device_e8_blocks() { return g_last_device_e8_blocks.load(std::memory_order_relaxed); }
+
 int device_codes_mode() {
   const char* knob = getenv("ZPAQ_AMD_DEVICE_CODES");
   return !knob || !knob[0] ? 2 : (knob[0] != '0' ? 1 : 0);
@@ -271,6 +281,22 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
   std::vector<std::vector<U32>> dev_sa(nb);
   std::vector<SortOut> dev_pre(nb);
   std::vector<char> have_pre(nb, 0);
+  // E8E9 of a block that takes one of the device routes below runs there as well when ZPAQ_AMD_DEVICE_E8 or the route's rule says
+  // so (SortJob::e8): the uploaded copy is filtered before the sort or the parse reads it and the filtered bytes
+  // come down into the caller's buffer, which ends up as the reference leaves it whichever side filtered.  e8_state[b] says what
+  // in[b].data holds (kE8Not .. kE8InFlight, device/engine.hpp); after_route() filters on the host what the device did not get
+  // to, and passes on the error of a download that failed -- that buffer is in no known state, no fallback may read it.
+  const int e8_mode = device_e8_mode();
+  std::vector<U8> e8_state(nb, kE8Not);
+  std::exception_ptr route_error;                      // what the route's call threw, if it threw
+  const auto after_route = [&](const std::vector<size_t>& which) {
+    for (size_t b : which) if (e8_state[b] == kE8InFlight && route_error) std::rethrow_exception(route_error);
+    route_error = nullptr;
+    parallel_blocks(which.size(), [&](size_t k) {
+      const size_t b = which[k];
+      if (front[b].args[1] > 4 && e8_state[b] == kE8Not) { e8e9_forward(in[b].data, in[b].n); e8_state[b] = kE8Host; }
+    });
+  };
   {
     // Blocks of 2^24 bytes and more are beyond the batched sorter's 24-bit rank fields; they go to the wide sorter
     // (device/sa_wide_kernel.h), each on its own -- one such block fills the device, the four-block threshold below
@@ -297,14 +323,18 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
       const bool take = in[b].n >= wide_from && (wide_mode == 1 || (wide_mode == 2 && in[b].n >= (1u << 24) && sa_wide_pays(in[b].n)));
       if (!take && in[b].n < (1u << 24)) { sorting.push_back(b); sort_bytes += in[b].n; continue; }
       if (!take || engine_device_count() <= 0) { front[b].sorts = false; continue; }   // nothing was done up front: preprocess_block does it all
-      if (front[b].args[1] > 4) e8e9_forward(in[b].data, in[b].n);
+      const bool e8_there = front[b].args[1] > 4 && (e8_mode == 1 || (e8_mode == 2 && e8_forward_wide_pays(in[b].n)));
+      SortJob wj = sort_job(in[b].data, in[b].n, front[b].args);
+      if (e8_there) wj.e8 = &e8_state[b];
+      else if (front[b].args[1] > 4) { e8e9_forward(in[b].data, in[b].n); e8_state[b] = kE8Host; }
       SortOut so;
       std::string note;
       bool got = false;
       const bool parse_there = dev_parse && (front[b].args[1] & 3) != 3 &&
                                (parse_wide_mode == 1 || (parse_wide_mode == 2 && in[b].n >= (1u << 24) && lz_wide_parse_pays(in[b].n)));
-      try { got = engine_sort_wide(sort_job(in[b].data, in[b].n, front[b].args), so, note, !dev_parse, parse_there ? dev_codes : -1); }
-      catch (const Failure&) { got = false; }        // (any device trouble: the host sorts)
+      try { got = engine_sort_wide(wj, so, note, !dev_parse, parse_there ? dev_codes : -1); }
+      catch (const Failure&) { got = false; route_error = std::current_exception(); }        // (any device trouble: the host sorts)
+      if (e8_there) after_route(std::vector<size_t>(1, b));
       if (got && (!so.bwt.empty() || so.parsed)) { wide_parsed += so.parsed; coded_blocks += so.coded; dev_pre[b] = std::move(so); have_pre[b] = 1; }
       else if (got) dev_sa[b].swap(so.sa);
       wide_blocks += got;                            // (front[b].sorts stays true: E8E9 is done either way)
@@ -316,18 +346,27 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     bool in_range = sorting.size() <= 65535 && sort_bytes < (1ull << 31);
     for (size_t b : sorting) in_range = in_range && in[b].n < (1u << 24);
     if (in_range && sorting.size() >= 4 && sort_bytes >= (1u << 20) && engine_device_count() > 0) {
-      parallel_blocks(sorting.size(), [&](size_t k) {        // E8E9 first where the method has it: it changes the bytes that are sorted
-        const size_t b = sorting[k];
-        if (front[b].args[1] > 4) e8e9_forward(in[b].data, in[b].n);
-      });
+      const char* knob = getenv("ZPAQ_AMD_DEVICE_PARSE");
+      U64 e8_n = 0, e8_bytes = 0;
+      for (size_t b : sorting) if (front[b].args[1] > 4) { ++e8_n; e8_bytes += in[b].n; }
+      // (the sort alone, with ZPAQ_AMD_DEVICE_PARSE=0, takes the blocks as they are: the host filters)
+      const bool e8_there = (!knob || knob[0] != '0') && (e8_mode == 1 || (e8_mode == 2 && e8_forward_pays(e8_n, e8_bytes)));
+      if (!e8_there)
+        parallel_blocks(sorting.size(), [&](size_t k) {      // E8E9 first where the method has it: it changes the bytes that are sorted
+          const size_t b = sorting[k];
+          if (front[b].args[1] > 4) { e8e9_forward(in[b].data, in[b].n); e8_state[b] = kE8Host; }
+        });
       std::string note;
       bool got = false;
-      const char* knob = getenv("ZPAQ_AMD_DEVICE_PARSE");
       if (!knob || knob[0] != '0') {
         std::vector<SortJob> sj;
-        for (size_t b : sorting) sj.push_back(sort_job(in[b].data, in[b].n, front[b].args));
+        for (size_t b : sorting) {
+          sj.push_back(sort_job(in[b].data, in[b].n, front[b].args));
+          if (e8_there && front[b].args[1] > 4) sj.back().e8 = &e8_state[b];
+        }
         std::vector<SortOut> so;
-        try { got = engine_sort_preprocess(sj, so, note, dev_codes); } catch (const Failure&) { got = false; }   // (any device trouble: the next path)
+        try { got = engine_sort_preprocess(sj, so, note, dev_codes); } catch (const Failure&) { got = false; route_error = std::current_exception(); }   // (any device trouble: the next path)
+        if (e8_there) after_route(sorting);
         if (got)
           for (size_t k = 0; k < sorting.size(); ++k) { coded_blocks += so[k].coded; dev_pre[sorting[k]] = std::move(so[k]); have_pre[sorting[k]] = 1; }
       }
@@ -359,16 +398,24 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     const char* knob = getenv("ZPAQ_AMD_DEVICE_PARSE");
     if (in_range && (!knob || knob[0] != '0') && hashing.size() >= kHashParseMinBlocks && hash_bytes >= kHashParseMinBytes &&
         engine_device_count() > 0) {
-      parallel_blocks(hashing.size(), [&](size_t k) {
-        const size_t b = hashing[k];
-        if (front[b].args[1] > 4) e8e9_forward(in[b].data, in[b].n);
-      });
+      U64 e8_n = 0, e8_bytes = 0;
+      for (size_t b : hashing) if (front[b].args[1] > 4) { ++e8_n; e8_bytes += in[b].n; }
+      const bool e8_there = e8_mode == 1 || (e8_mode == 2 && e8_forward_pays(e8_n, e8_bytes));
+      if (!e8_there)
+        parallel_blocks(hashing.size(), [&](size_t k) {
+          const size_t b = hashing[k];
+          if (front[b].args[1] > 4) { e8e9_forward(in[b].data, in[b].n); e8_state[b] = kE8Host; }
+        });
       std::vector<SortJob> hj;
-      for (size_t b : hashing) hj.push_back(hash_job(in[b].data, in[b].n, front[b].args));
+      for (size_t b : hashing) {
+        hj.push_back(hash_job(in[b].data, in[b].n, front[b].args));
+        if (e8_there && front[b].args[1] > 4) hj.back().e8 = &e8_state[b];
+      }
       std::vector<SortOut> ho;
       std::string note;
       bool got = false;
-      try { got = engine_hash_preprocess(hj, ho, note, dev_codes); } catch (const Failure&) { got = false; }      // (any device trouble: the host parses)
+      try { got = engine_hash_preprocess(hj, ho, note, dev_codes); } catch (const Failure&) { got = false; route_error = std::current_exception(); }      // (any device trouble: the host parses)
+      if (e8_there) after_route(hashing);
       if (got)
         for (size_t k = 0; k < hashing.size(); ++k) { coded_blocks += ho[k].coded; dev_pre[hashing[k]] = std::move(ho[k]); have_pre[hashing[k]] = 1; }
       for (size_t b : hashing) front[b].sorts = true;                 // (E8E9 is done either way)
@@ -376,6 +423,7 @@ void compress_blocks(const char* method, const std::vector<BlockInput>& in, bool
     }
   }
   tm.device_coded_blocks = coded_blocks;
+  g_last_device_e8_blocks.store((U32)std::count(e8_state.begin(), e8_state.end(), (U8)kE8Device), std::memory_order_relaxed);
   parallel_blocks(nb, [&](size_t b) {
     Work& w = work[b];
     const Front& f = front[b];

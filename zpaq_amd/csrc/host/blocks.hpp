@@ -71,6 +71,8 @@ U32 last_device_unlz_wide_segments();   // ... that device/lz77_decode_wide_kern
 U32 last_device_unbwt_segments();
 // ... that went through their stage's decoder and device/e8e9_kernel.h (the E8E9 methods)
 U32 last_device_une8_segments();
+// blocks of this process's last compress_blocks call whose forward E8E9 filter ran on the device (ZPAQ_AMD_DEVICE_E8)
+U32 last_device_e8_blocks();
 // ... of x.,5 / x.,6 groups that went through device/lz77_decode_wide_kernel.h and device/e8e9_kernel.h (not counted above)
 U32 last_device_une8_wide_segments();
 // ... that ran their block's own PCOMP program on the device (device/pcomp_kernel.h through engine_pcomp)
